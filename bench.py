@@ -46,7 +46,7 @@ from benchlib.common import HBM_PEAK_GBS, PROF_EVERY  # noqa: E402,F401
 from benchlib.ddself import run_dd_self  # noqa: E402
 from benchlib.eds import run_eds  # noqa: E402
 from benchlib.generic import run_generic_lj  # noqa: E402
-from benchlib.md import run_md  # noqa: E402
+from benchlib.md import MD_WORKLOADS, run_md  # noqa: E402
 from benchlib.small import run_ref_lj256, run_small  # noqa: E402
 
 
@@ -83,8 +83,8 @@ def parse():
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="N > 1: strong = the --cells box itself cut into N slabs (default; the BASELINE metric), "
                          "weak = N such boxes side by side, one per rank (config 5)")
-    ap.add_argument("--windows", type=int, default=0,
-                    help="timed windows of --steps steps each; `value` is their median (0 = 5 windows when --steps <= 50, else 1)")
+    ap.add_argument("--windows", type=int, default=1,
+                    help="timed windows of --steps steps each; `value` is their median (the default, 1: exactly --steps timed steps)")
     ap.add_argument("--host-nlist-decision", action="store_true",
                     help="read the neighbor-list distance check back to the host (round-1 behaviour); default: the "
                          "rebuild is gated on the device, the step loop never synchronises")
@@ -94,6 +94,9 @@ def parse():
                     help="HOOMD built in double precision: fp64 positions / velocities / forces on the wire, fp32 pair vectors "
                          "and model arithmetic (the reference casts the fp64 buffer to the model dtype, simmodel.py:226-238)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one handed its caller -- the force array (force, per-particle "
+                         "energy), the new positions and velocities -- as DIR/<name>.npy (one-rank MD workloads)")
     return ap.parse_args()
 
 
@@ -183,6 +186,8 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
+    if args.dump_outputs and (world > 1 or args.workload not in MD_WORKLOADS):
+        raise SystemExit("--dump-outputs: one rank and an MD workload (%s)" % ", ".join(MD_WORKLOADS))
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU: the evaluator has no CPU path")
     # HTF_BENCH_BACKEND=gloo: rehearsal of the multi-rank code path with several ranks on ONE
@@ -228,7 +233,7 @@ def main():
         return run_small(args, htf, standin, dev)
     headline = args.workload == "lj" and not args.f64 and not args.two_kernel
     E.live = None
-    out = run_md(args, E, args.workload, variants=not args.no_fused, cpu=not args.no_cpu_baseline)
+    out = run_md(args, E, args.workload, variants=not args.no_fused, cpu=not args.no_cpu_baseline, dump_dir=args.dump_outputs)
     live = E.live          # the LJ run's objects, for the guarded multi-rank section below
     if headline and not args.no_mlp and ((world == 1 and args.cells == 32) or (world > 1 and args.scaling == "strong")):
         # north_star: "LJ AND MLP pair-potential boxes ... at 1/2/4/8": the same C3 system driven by the pair-MLP in its default

@@ -11,9 +11,29 @@ import torch
 from .common import HBM_PEAK_GBS, PROF_EVERY, ROOT, algorithmic_bytes, gpu_state, make_potential  # noqa: F401
 from .cpu import cpu_baseline
 
+MD_WORKLOADS = ("lj", "wca", "mlp", "mlp-fp32", "mlp-split", "mlp-bf16", "mlp-train")
+DUMP_LIMIT_BYTES = 64 << 20
 
-def run_md(args, E, workload, variants=True, cpu=True, keep_live=True):
-    """One MD workload (lj | wca | mlp | mlp-split | mlp-bf16 | mlp-train) on this job's ranks -> the JSON record."""
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """``arrays`` (name -> tensor, one row per particle) as out_dir/<name>.npy.  Past DUMP_LIMIT_BYTES in all, every array keeps
+    the same seeded sample of rows, in order, and sample_rows.npy holds their indices (float64: exact)."""
+    host = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    assert all(a.dtype in (np.float32, np.float64) for a in host.values()), {k: a.dtype for k, a in host.items()}
+    n = len(next(iter(host.values())))
+    per_row = sum(a.nbytes for a in host.values()) / max(n, 1)
+    room = DUMP_LIMIT_BYTES - 4096 * (len(host) + 1)     # (each .npy file's header)
+    if per_row * n > room:
+        rows = np.sort(np.random.default_rng(seed).choice(n, int(room // (per_row + 8)), replace=False))
+        host = dict({k: a[rows] for k, a in host.items()}, sample_rows=rows.astype(np.float64))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
+def run_md(args, E, workload, variants=True, cpu=True, keep_live=True, dump_dir=None):
+    """One MD workload (lj | wca | mlp | mlp-split | mlp-bf16 | mlp-train) on this job's ranks -> the JSON record.  ``dump_dir``:
+    what the last timed step handed its caller is written there (dump_outputs)."""
     import copy
     args = copy.copy(args)
     args.workload = workload
@@ -258,9 +278,9 @@ def run_md(args, E, workload, variants=True, cpu=True, keep_live=True):
     # launch costs the 0.1 ms step about 8 %
     ctx.profile_enable(PROF_EVERY)
     batches_per_step = 2 if (nl.domain is not None and world > 1 and nl.domain.n_interior > 0) else 1
-    # `value` = median over the windows: a 20-step window is 2 ms and holds one to three neighbor-list
-    # rebuilds (~0.25 ms each), so a single short window swings by +-10 % with where the rebuilds fall
-    n_windows = args.windows if args.windows > 0 else (5 if args.steps <= 50 else 1)
+    # `value` = median over the windows (--windows, default 1: exactly --steps timed steps).  A 20-step window is 2 ms and holds
+    # one to three neighbor-list rebuilds (~0.25 ms each), so a single short window swings by +-10 % with where the rebuilds fall
+    n_windows = max(args.windows, 1)
     builds0 = builds_now()
     windows, window_prof = [], []
     for _ in range(n_windows):
@@ -271,6 +291,10 @@ def run_md(args, E, workload, variants=True, cpu=True, keep_live=True):
     build_ms, eval_ms, ncalls = window_prof[int(np.argsort(windows)[len(windows) // 2])]
     ctx.profile_enable(False)
     rebuilds = (builds_now() - builds0) / n_windows  # per window of args.steps steps
+    if dump_dir:
+        # the last timed step's results as the caller holds them: the force array (force xyz, per-particle energy) of the step's
+        # positions, and the positions and velocities the integrator moved on to (xyz: .w holds the type bits and the mass)
+        dump_outputs(dump_dir, {"force": sysm.force[:sysm.N], "position": sysm.pos[:sysm.N, :3], "velocity": sysm.vel[:sysm.N, :3]})
     # clocks / power cap WHILE the loop runs: an extra, untimed stretch of steps with the sysfs read in its middle (behind a
     # synchronize the part has already clocked down: 158 MHz)
     for _ in range(30):

@@ -131,7 +131,7 @@ def guarded_section(E, live, out, emit):
     res = {}
     wd = PhaseWatchdog(E.rank, lambda why: emit(dict(res, guarded_section_ended_by=why)))
     steps = max(args.steps, P) // P * P
-    windows = args.windows if args.windows > 0 else (5 if args.steps <= 50 else 1)
+    windows = max(args.windows, 1)
 
     def phase(name, fn, seconds=limit):
         """Run fn() on every rank under the watchdog; -> (ok on every rank, this rank's result or error text)."""

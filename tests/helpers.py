@@ -14,6 +14,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+# At most six processes may hold the GPU at once, and the pytest process that starts a test's rank processes holds it already:
+# a test that shares the one GPU between rank processes starts at most five of them.
+MAX_RANKS = 5
+
+
+def check_rank_count(world):
+    assert world <= MAX_RANKS, "%d rank processes on one GPU: at most %d beside the test process" % (world, MAX_RANKS)
+
 
 def sq_lattice(n, a, dtype=np.float64):
     """hoomd.lattice.sq(a) replicated n x n: 2-D, box (n a, n a, 1), centred."""

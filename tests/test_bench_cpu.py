@@ -42,3 +42,25 @@ def test_the_faster_of_two_verified_replays_wins():
     line["graph_variant"] = dict(line["graph_variant_peer"], value=9100.0, ms_per_step=1 / 9.1, halo={"transport": "native"})
     d = multirank.promote_verified(line)
     assert d["value"] == 9100.0 and "'native'" in d["value_path"]
+
+
+def test_dumped_outputs_stay_within_the_limit_as_one_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: arrays as written while they fit; past the limit every array keeps the SAME seeded rows, in order."""
+    import numpy as np
+    import torch
+    from benchlib import md
+    f = torch.randn((1000, 4), dtype=torch.float32)
+    p = torch.randn((1000, 3), dtype=torch.float64)
+    md.dump_outputs(str(tmp_path / "all"), {"force": f, "position": p})
+    assert sorted(x.name for x in (tmp_path / "all").iterdir()) == ["force.npy", "position.npy"]
+    assert np.array_equal(np.load(tmp_path / "all" / "force.npy"), f.numpy())
+    monkeypatch.setattr(md, "DUMP_LIMIT_BYTES", 40000)
+    for d in ("s1", "s2"):
+        md.dump_outputs(str(tmp_path / d), {"force": f, "position": p})
+    assert sum(x.stat().st_size for x in (tmp_path / "s1").iterdir()) <= 40000
+    rows = np.load(tmp_path / "s1" / "sample_rows.npy")
+    assert rows.dtype == np.float64 and 0 < len(rows) < 1000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(rows, np.load(tmp_path / "s2" / "sample_rows.npy"))
+    r = rows.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "s1" / "force.npy"), f.numpy()[r])
+    assert np.array_equal(np.load(tmp_path / "s1" / "position.npy"), p.numpy()[r])

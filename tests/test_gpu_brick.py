@@ -1,5 +1,6 @@
 """BrickDomain on the GPU: csrc/brick.hip against its torch restatement, the replica mode against the replicated single-domain
-system, slabs against SlabDomain bit for bit, a 4 x 2 cut against the single-domain forces (ranks share the one GPU over gloo)."""
+system, slabs against SlabDomain bit for bit, 2 x 2 and 5 x 1 cuts against the single-domain forces (ranks share the one GPU over
+gloo)."""
 import os
 import socket
 import sys
@@ -10,7 +11,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-from helpers import ROOT
+from helpers import ROOT, check_rank_count
 
 pytestmark = pytest.mark.gpu
 
@@ -249,47 +250,42 @@ def _slab_twin_worker(rank, world, port, q, per_slab):
         q.put((rank, traceback.format_exc()))
 
 
-def _run_ranks(target, world, args, timeout=900, attempts=2):
-    """The ranks SHARE this GPU: up to eight processes are time-sliced on it, each with spinning wait kernels of the library-free
-    transport in flight, and on a cold box their start-up is seconds apart.  Every wait is bounded -- ~4 s of polling on the device
-    (HTF_PEER_SPIN), 30 s on the host for a replayed cycle (HTF_BRICK_WAIT_S) -- which an oversubscribed rehearsal now and then
-    exceeds (seen twice in ~10 runs of the whole suite, never with the test alone): a rehearsal gets 30 s / 120 s, and ONE more
-    attempt when the failure is such a wait running out.  Anything else fails at once."""
+def _run_ranks(target, world, args, timeout=900):
+    """The ranks SHARE this GPU: up to five processes are time-sliced on it beside this one (helpers.MAX_RANKS), each with
+    spinning wait kernels of the library-free transport in flight, and on a cold box their start-up is seconds apart.  Every wait
+    is bounded -- ~4 s of polling on the device (HTF_PEER_SPIN), 30 s on the host for a replayed cycle (HTF_BRICK_WAIT_S) -- so a
+    rehearsal gets 30 s / 120 s.  One attempt: a wait that runs out fails the test."""
+    check_rank_count(world)
     saved = {k: os.environ.get(k) for k in ("HTF_PEER_SPIN", "HTF_BRICK_WAIT_S")}
     for k, v in (("HTF_PEER_SPIN", str(1 << 25)), ("HTF_BRICK_WAIT_S", "120")):
         if saved[k] is None:
             os.environ[k] = v
     try:
-        for attempt in range(attempts):
-            ctx = mp.get_context("spawn")
-            q = ctx.Queue()
-            port = _free_port()
-            procs = [ctx.Process(target=target, args=(r, world, port, q) + tuple(args)) for r in range(world)]
-            for p in procs:
-                p.start()
-            results = [q.get(timeout=timeout) for _ in procs]
-            for p in procs:
-                p.join(timeout=60)
-                if p.is_alive():
-                    p.kill()
-            bad = [res for res in results if res[1] != "ok"]
-            waits = ("never reached cycle", "did not arrive", "timed out", "Timeout")
-            if bad and attempt + 1 < attempts and all(any(w in str(res[1]) for w in waits) or "another rank" in str(res[1]) for res in bad) \
-                    and any(any(w in str(res[1]) for w in waits) for res in bad):
-                continue
-            for res in results:
-                assert res[1] == "ok", "rank %d failed:\n%s" % (res[0], res[1])
-            return results
+        ctx = mp.get_context("spawn")
+        q = ctx.Queue()
+        port = _free_port()
+        procs = [ctx.Process(target=target, args=(r, world, port, q) + tuple(args)) for r in range(world)]
+        for p in procs:
+            p.start()
+        results = [q.get(timeout=timeout) for _ in procs]
+        for p in procs:
+            p.join(timeout=60)
+            if p.is_alive():
+                p.kill()
+        for res in results:
+            assert res[1] == "ok", "rank %d failed:\n%s" % (res[0], res[1])
+        return results
     finally:
         for k, v in saved.items():
             if v is None:
                 os.environ.pop(k, None)
 
 
-@pytest.mark.parametrize("world,per_slab", [(3, 4), (8, 2)])
+@pytest.mark.parametrize("world,per_slab", [(3, 4), (5, 2)])
 def test_brick_slabs_equal_slab_domain_bit_for_bit(htf, cuda, world, per_slab):
     """fixed-capacity arrays with inert rows and device-resident counts change nothing a particle sees --
-    trajectories bit-identical to SlabDomain's at world 3 and at world 8 (slabs thinner than 2 r_ghost)."""
+    trajectories bit-identical to SlabDomain's at world 3 and at world 5 (slabs thinner than 2 r_ghost, so a rank's ghosts come
+    from both neighbors on each side, four distinct ranks)."""
     _run_ranks(_slab_twin_worker, world, (per_slab,))
 
 
@@ -346,7 +342,7 @@ def _brick_md_worker(rank, world, port, q, grid, cells, transport="torch", repla
         assert nl.n_builds >= 2 and overlapped >= 20, (nl.n_builds, overlapped)
         assert (dom.n_light > 0) == (replan_every > 1), dom.n_light
         c = dom.counts_host()
-        assert int(c[_lib.BC_N_INT]) > 0                         # a 2-D cut keeps interior rows
+        assert int(c[_lib.BC_N_INT]) > 0                         # bricks wider than 2 r_ghost keep interior rows
         live = dom.live_rows()
         my_ids = sysm.pos[live, 3].contiguous().view(torch.int32).cpu().numpy()
         loc = torch.zeros((Ng, 3), dtype=torch.float64)
@@ -386,10 +382,12 @@ def test_bricks_with_the_peer_transport(htf, cuda, grid, cells):
     _run_ranks(_brick_md_worker, grid[0] * grid[1], (grid, cells, "peer"))
 
 
-@pytest.mark.parametrize("grid,cells", [((4, 2, 1), (16, 8, 5)), ((2, 2, 1), (8, 8, 5)), ((3, 1, 1), (12, 5, 5))])
+@pytest.mark.parametrize("grid,cells", [((5, 1, 1), (20, 5, 5)), ((2, 2, 1), (8, 8, 5)), ((3, 1, 1), (12, 5, 5))])
 def test_bricks_on_one_gpu(htf, cuda, grid, cells):
-    """8 ranks as 4 x 2 (bricks 6.7 x 6.7 sigma against r_ghost 2.9: interior rows), 80 MD steps, forces ==
-    single-domain (test_mpi_tensorflow.py:57-79, ``comm.decomposition(nx=4, ny=2)``)."""
+    """5 ranks as 5 x 1 and 4 as 2 x 2 (bricks 6.7 sigma wide against r_ghost 2.9: interior rows), 80 MD steps,
+    forces == single-domain (test_mpi_tensorflow.py:57-79, ``comm.decomposition``).  The 4 x 2 cut of eight ranks would need more
+    processes on the one GPU than it may hold (helpers.MAX_RANKS); replica mode runs it
+    (test_replica_brick_forces_equal_the_replicated_box)."""
     _run_ranks(_brick_md_worker, grid[0] * grid[1], (grid, cells))
 
 
@@ -521,11 +519,11 @@ def _peer_replay_worker(rank, world, port, q, grid, cells, replan_every, die_at=
         q.put((rank, traceback.format_exc()))
 
 
-@pytest.mark.parametrize("grid,cells,replan", [((3, 1, 1), (12, 5, 5), 1), ((2, 2, 1), (10, 10, 5), 2), ((4, 2, 1), (16, 10, 5), 2)])
+@pytest.mark.parametrize("grid,cells,replan", [((3, 1, 1), (12, 5, 5), 1), ((2, 2, 1), (10, 10, 5), 2), ((5, 1, 1), (20, 5, 5), 2)])
 def test_replayed_cycles_between_processes_with_the_peer_transport(htf, cuda, grid, cells, replan):
     """a decomposed run between real ranks with NO communication library -- halo, migration messages and the
     all-reduced distance check are stores into the neighbors' fine-grained memory -- eager and replayed from hipGraphs (three per
-    rank with replan_every = 2), bit-identical, forces == single-domain.  3 slabs, 2 x 2, and 4 x 2 = 8 processes."""
+    rank with replan_every = 2), bit-identical, forces == single-domain.  3 slabs, 2 x 2, and 5 slabs (helpers.MAX_RANKS)."""
     _run_ranks(_peer_replay_worker, grid[0] * grid[1], (grid, cells, replan))
 
 
@@ -539,6 +537,7 @@ def test_a_rank_that_dies_is_noticed_by_every_other_rank(htf, cuda):
     env_before = os.environ.get("HTF_PEER_SPIN")
     os.environ["HTF_PEER_SPIN"] = "40000"          # ~0.1 s of polling per missing message (children inherit it)
     try:
+        check_rank_count(4)
         procs = [ctx.Process(target=_peer_replay_worker, args=(r, 4, port, q, (4, 1, 1), (16, 5, 5), 1, (1, 30))) for r in range(4)]
         for p in procs:
             p.start()

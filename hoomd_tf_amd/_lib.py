@@ -242,6 +242,14 @@ STANDIN_PROTOTYPES = {
                                       _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp]),
 }
 
+# coarse-grained mapping ops (include/htf_cg.h): center_of_mass, compute_nlist (hoomd_tf_amd/cgmap.py)
+CG_PROTOTYPES = {
+    "htf_cg_com_forward": (_i, [_vp, _u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "htf_cg_com_backward": (_i, [_vp, _u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "htf_cg_nlist_forward": (_i, [_vp, _u, _u, _vp, C.c_float, _u, _i, _i, _vp, _vp, _vp, _vp]),
+    "htf_cg_nlist_backward": (_i, [_vp, _u, _u, _vp, _vp, _vp]),
+}
+
 
 ABI_VERSION = 4  # include/htf_amd.h HTF_AMD_ABI_VERSION: the struct layouts the ctypes Structures of this file mirror
 
@@ -252,7 +260,7 @@ def _load():
             "hoomd_tf_amd: %s is missing. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C hoomd_tf_amd/csrc`. There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(PROTOTYPES.items()) + list(STANDIN_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(STANDIN_PROTOTYPES.items()) + list(CG_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -296,7 +304,7 @@ class _PybindLib:
 
     def __init__(self, mod):
         self._mod = mod
-        for name, (res, args) in list(PROTOTYPES.items()) + list(STANDIN_PROTOTYPES.items()):
+        for name, (res, args) in list(PROTOTYPES.items()) + list(STANDIN_PROTOTYPES.items()) + list(CG_PROTOTYPES.items()):
             fn = getattr(mod, name)  # AttributeError if the module lacks a declared symbol
             ptr_at = tuple(i for i, t in enumerate(args) if _is_pointer(t))
             setattr(self, name, self._wrap(fn, ptr_at, res is _vp))

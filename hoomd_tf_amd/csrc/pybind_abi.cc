@@ -14,6 +14,7 @@
 
 #include "htf_amd.h"
 #include "htf_standin.h"
+#include "htf_cg.h"
 
 namespace py = pybind11;
 
@@ -154,6 +155,13 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
     X(htfs_brick_pack_halo_peer) \
     X(htfs_brick_unpack_halo)
 
+// include/htf_cg.h: the coarse-grained ops (_lib.CG_PROTOTYPES)
+#define HTF_CG_FUNCTIONS(X) \
+    X(htf_cg_com_forward) \
+    X(htf_cg_com_backward) \
+    X(htf_cg_nlist_forward) \
+    X(htf_cg_nlist_backward)
+
 PYBIND11_MODULE(_htf_abi, m) {
     m.doc() = "pybind11 binding of libhtf_amd.so's C ABI: pointers as integers";
     // a stale module (or library): this module's templates were instantiated from one header, the library it resolved at load
@@ -164,5 +172,6 @@ PYBIND11_MODULE(_htf_abi, m) {
     m.attr("abi_version") = HTF_AMD_ABI_VERSION;
 #define X(fn) bind(m, #fn, &fn);
     HTF_ABI_FUNCTIONS(X)
+    HTF_CG_FUNCTIONS(X)
 #undef X
 }

@@ -651,13 +651,16 @@ class Simulation:
         self.forces = []     # hoomd.context.current.forces
         self.computes = []   # system.addCompute(...) without forces
         self.integrator = None
+        self.nlists = []     # the neighbor lists made by nlist_cell (center_of_mass asks whether one sorts particles)
         _current["sim"] = self
 
     def nlist_cell(self, r_buff=0.4, check_period=1, pitch=None, device_decision=True):
         """hoomd.md.nlist.cell(): r_cut comes from the subscribers (nlist.subscribe).  The rebuild decision stays
         on the device (CellNlist.device_decision) wherever the list qualifies: one rank, no particle sorter."""
-        return CellNlist(self.system, r_cut=0.0, r_buff=r_buff, pitch=pitch, check_period=check_period,
-                         device_decision=device_decision)
+        nl = CellNlist(self.system, r_cut=0.0, r_buff=r_buff, pitch=pitch, check_period=check_period,
+                       device_decision=device_decision)
+        self.nlists.append(nl)
+        return nl
 
     def integrate_nve(self, dt, group=None):
         self.integrator = NVE(self.system, dt, group=group)

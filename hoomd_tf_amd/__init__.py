@@ -4,7 +4,8 @@ Mirrors the reference's Python surface for that path (``hoomd.htf``): ``SimModel
 ``tfcompute``, ``compute_nlist_forces``, ``nlist_rinv``, ``safe_norm``,
 ``RBFExpansion``, ``WCARepulsion``, ``EDSLayer`` ...  All arithmetic runs in the
 hand-written HIP kernels of ``libhtf_amd.so`` (C ABI: include/htf_amd.h; the coarse-grained mapping ops
-``center_of_mass`` / ``compute_nlist``: include/htf_cg.h).
+``center_of_mass`` / ``compute_nlist``: include/htf_cg.h; the molecular geometry ops ``mol_bond_distance`` / ``mol_angle`` /
+``mol_dihedral``: include/htf_geom.h).
 """
 from . import _lib
 from ._lib import NlistOverflowError, SkewedBoxError
@@ -19,6 +20,7 @@ from .simmodel import (SimModel, compute_nlist_forces, compute_positions_forces,
 from .layers import RBFExpansion, WCARepulsion, EDSLayer, PairMLP, SoftRDFCV, LJLayer, Dense
 from . import optimizers
 from .cgmap import sparse_mapping, center_of_mass, compute_nlist
+from .molgeom import mol_bond_distance, mol_angle, mol_dihedral, mol_features_multiple
 from .tensorflowcompute import tfcompute
 
 __version__ = "0.1.0"

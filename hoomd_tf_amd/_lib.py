@@ -250,6 +250,14 @@ CG_PROTOTYPES = {
     "htf_cg_nlist_backward": (_i, [_vp, _u, _u, _vp, _vp, _vp]),
 }
 
+# molecular geometry ops (include/htf_geom.h): mol_bond_distance, mol_angle, mol_dihedral (hoomd_tf_amd/molgeom.py)
+GEOM_PROTOTYPES = {
+    "htf_geom_mol_forward": (_i, [_vp, _u, _u, _u, _u, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "htf_geom_mol_backward": (_i, [_vp, _u, _u, _u, _u, _i, _i, _i, _i, _vp, _vp, _u, _vp, _vp]),
+    "htf_geom_cg_forward": (_i, [_vp, _u, _u, _u, _u, _vp, _vp, _vp, _vp]),
+    "htf_geom_cg_backward": (_i, [_vp, _u, _u, _u, _u, _vp, _vp, _vp, _vp, _vp, _u, _vp, _vp, _vp]),
+}
+
 
 ABI_VERSION = 4  # include/htf_amd.h HTF_AMD_ABI_VERSION: the struct layouts the ctypes Structures of this file mirror
 
@@ -260,7 +268,8 @@ def _load():
             "hoomd_tf_amd: %s is missing. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C hoomd_tf_amd/csrc`. There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(PROTOTYPES.items()) + list(STANDIN_PROTOTYPES.items()) + list(CG_PROTOTYPES.items()):
+    for name, (res, args) in (list(PROTOTYPES.items()) + list(STANDIN_PROTOTYPES.items()) + list(CG_PROTOTYPES.items())
+                              + list(GEOM_PROTOTYPES.items())):
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -304,7 +313,8 @@ class _PybindLib:
 
     def __init__(self, mod):
         self._mod = mod
-        for name, (res, args) in list(PROTOTYPES.items()) + list(STANDIN_PROTOTYPES.items()) + list(CG_PROTOTYPES.items()):
+        for name, (res, args) in (list(PROTOTYPES.items()) + list(STANDIN_PROTOTYPES.items()) + list(CG_PROTOTYPES.items())
+                                  + list(GEOM_PROTOTYPES.items())):
             fn = getattr(mod, name)  # AttributeError if the module lacks a declared symbol
             ptr_at = tuple(i for i, t in enumerate(args) if _is_pointer(t))
             setattr(self, name, self._wrap(fn, ptr_at, res is _vp))

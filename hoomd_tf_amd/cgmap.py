@@ -62,18 +62,35 @@ def sparse_mapping(molecule_mapping, molecule_mapping_index, system=None, device
 
 
 # ---------------------------------------------------------------------------------------------- centre of mass
-_MAPS = {}   # id(mapping) -> (weakref, device, _version, arrays): the CSR / CSC copies on the device
+_MAPS = {}   # (tag, id(tensor), ...) -> (weakrefs, device, _versions, extra, arrays): device arrays derived from tensors
+
+
+def _cached(tag, tensors, device, build, extra=None):
+    """``build()``'s arrays for ``tensors`` on ``device``, built on first use and whenever one tensor's ``_version`` (or
+    ``extra``) changes; kept while the tensors live.  A hit touches nothing on the device."""
+    key = (tag,) + tuple(id(t) for t in tensors)
+    versions = tuple(t._version for t in tensors)
+    hit = _MAPS.get(key)
+    alive = hit is not None and all(r() is t for r, t in zip(hit[0], tensors))
+    if alive and hit[1] == device and hit[2] == versions and hit[3] == extra:
+        return hit[4]
+    arrays = build()
+    if not alive:
+        for t in tensors:
+            weakref.finalize(t, _MAPS.pop, key, None)
+    _MAPS[key] = (tuple(weakref.ref(t) for t in tensors), device, versions, extra, arrays)
+    return arrays
 
 
 def _device_maps(mapping, device):
     """The CSR and CSC copies of ``mapping`` on ``device``, built on first use and whenever the tensor's ``_version``
     changes; kept while the mapping tensor lives.  A hit touches nothing on the device."""
-    key = id(mapping)
-    hit = _MAPS.get(key)
-    if hit is not None and hit[0]() is mapping and hit[1] == device and hit[2] == mapping._version:
-        return hit[3]
     if not isinstance(mapping, torch.Tensor) or mapping.dim() != 2:
         raise ValueError("mapping must be a 2-d torch tensor (sparse_mapping), got %r" % type(mapping))
+    return _cached("mapping", (mapping,), device, lambda: _build_maps(mapping, device))
+
+
+def _build_maps(mapping, device):
     m = mapping if mapping.layout == torch.sparse_coo else mapping.to_sparse()
     m = m.coalesce()
     B, N = int(m.shape[0]), int(m.shape[1])
@@ -86,13 +103,9 @@ def _device_maps(mapping, device):
     row_ptr = torch.cat([zero, torch.cumsum(torch.bincount(rows, minlength=B), 0)]).to(torch.int32)
     order = torch.argsort(cols * max(B, 1) + rows)
     col_ptr = torch.cat([zero, torch.cumsum(torch.bincount(cols, minlength=N), 0)]).to(torch.int32)
-    arrays = {"B": B, "N": N, "row_ptr": row_ptr.contiguous(), "cols": cols.to(torch.int32).contiguous(), "vals": vals,
-              "col_ptr": col_ptr.contiguous(), "rows": rows[order].to(torch.int32).contiguous(),
-              "vals_c": vals[order].contiguous()}
-    if hit is None or hit[0]() is not mapping:
-        weakref.finalize(mapping, _MAPS.pop, key, None)
-    _MAPS[key] = (weakref.ref(mapping), device, mapping._version, arrays)
-    return arrays
+    return {"B": B, "N": N, "row_ptr": row_ptr.contiguous(), "cols": cols.to(torch.int32).contiguous(), "vals": vals,
+            "col_ptr": col_ptr.contiguous(), "rows": rows[order].to(torch.int32).contiguous(),
+            "vals_c": vals[order].contiguous()}
 
 
 _BOXES = {}

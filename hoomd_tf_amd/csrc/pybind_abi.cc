@@ -15,6 +15,7 @@
 #include "htf_amd.h"
 #include "htf_standin.h"
 #include "htf_cg.h"
+#include "htf_geom.h"
 
 namespace py = pybind11;
 
@@ -162,6 +163,13 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
     X(htf_cg_nlist_forward) \
     X(htf_cg_nlist_backward)
 
+// include/htf_geom.h: the molecular geometry ops (_lib.GEOM_PROTOTYPES)
+#define HTF_GEOM_FUNCTIONS(X) \
+    X(htf_geom_mol_forward) \
+    X(htf_geom_mol_backward) \
+    X(htf_geom_cg_forward) \
+    X(htf_geom_cg_backward)
+
 PYBIND11_MODULE(_htf_abi, m) {
     m.doc() = "pybind11 binding of libhtf_amd.so's C ABI: pointers as integers";
     // a stale module (or library): this module's templates were instantiated from one header, the library it resolved at load
@@ -173,5 +181,6 @@ PYBIND11_MODULE(_htf_abi, m) {
 #define X(fn) bind(m, #fn, &fn);
     HTF_ABI_FUNCTIONS(X)
     HTF_CG_FUNCTIONS(X)
+    HTF_GEOM_FUNCTIONS(X)
 #undef X
 }

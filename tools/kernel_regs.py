@@ -17,7 +17,7 @@ m = t._kernel_metadata(pathlib.Path(tempfile.mkdtemp()))
 names = sorted(m)
 dem = subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.strip().split("\n")
 for n, d in zip(names, dem):
-    short = d.split("(")[0]
+    short = d.replace("(anonymous namespace)::", "").split("(")[0]
     if all(a in short for a in args):
         v = m[n]
         print("%-70s vgpr %3d  sgpr_spill %3d  scratch %4d  lds %6d" % (short[-70:], v["vgpr_count"], v["sgpr_spill_count"],

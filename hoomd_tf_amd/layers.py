@@ -221,6 +221,7 @@ class PairMLP:
         self.params = mlp_params(seed=seed, K=K, H1=H1, H2=H2)
         self.w = None      # flat device weights (Keras get_weights() order) once the potential exists
         self._pot = None
+        self._seen = None  # self.w._version the operand images were last built from
 
     def _flat(self):
         return np.concatenate([np.asarray(self.params[k], dtype=np.float32).ravel() for k in self._KEYS])
@@ -240,11 +241,19 @@ class PairMLP:
         if self._pot is None:
             self._pot = ops.Potential.pair_mlp(self.params, self.low, self.high, activation=self.activation,
                                                precision=self.precision, theta=self.make_trainable())
+        self.refresh_if_stale()
         return self._pot
 
     def after_update(self):
         if self._pot is not None:
             self._pot.refresh()
+            self._seen = self.w._version
+
+    def refresh_if_stale(self):
+        """``self.w`` written by anybody but the training step (an in-place op on ``trainable_weights[0]``, an optimizer of the
+        user's own): the operand images are rebuilt from it before the next launch."""
+        if self._pot is not None and self._seen != self.w._version:
+            self.after_update()
 
     def _sync_host(self):
         if self.w is None:

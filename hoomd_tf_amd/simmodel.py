@@ -2061,6 +2061,7 @@ class SimModel:
             raise ValueError("loss %r is not built; available: 'MeanSquaredError'" % (first,))
         self.loss = list(loss) if isinstance(loss, (list, tuple)) else [loss]
         self.metrics = [_LossMetric()]
+        self._compiled = getattr(self, "_compiled", 0) + 1   # (tfcompute drops the old optimizer's descriptor, twin and moments)
 
     # ---- Keras weights API over whatever the model's layers hold (simmodel.py inherits it from tf.keras.Model)
     def _weight_holders(self):

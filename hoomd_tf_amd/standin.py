@@ -707,6 +707,8 @@ class Simulation:
             self._step()
             nsteps -= 1
         f, nl = self.forces[0], self.forces[0]._nlist
+        if hasattr(f, "pre_replay"):
+            f.pre_replay()     # weights written between runs: copied in now, neither recorded in the capture nor missed by the replay
         # (everything a captured launch carries by value: a change of any of it re-captures -- sizes, scalars, and the ADDRESS of
         #  every buffer the step touches: rebinding sysm.pos / vel, a list whose buffers were re-allocated)
         key = (id(f), id(nl), id(self.integrator), cycle, s.N, nl.pitch, f.graph_key(), float(self.integrator.dt), float(nl.r_list),

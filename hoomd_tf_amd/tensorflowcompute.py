@@ -68,7 +68,7 @@ class tfcompute:
         self.train = train
         self._ref_forces = []
         self._labels = None
-        self._opt_state = None
+        self._drop_optimizer_state()
         if isinstance(self.model, simmodel.MolSimModel):  # tensorflowcompute.py:103-111
             if self.batch_size != 0:
                 raise ValueError('Cannot batch by molecule and by batch_number')
@@ -97,6 +97,7 @@ class tfcompute:
         self.virial = torch.zeros(6 * s.N, dtype=s.dtype, device=s.device)
         self._plan = None
         self._plan_folded = ()   # (weight, _version) pairs whose values are constants of the plan's generated kernel
+        self._plan_weights = None  # weights the plan's kernels read at launch, copied in when written (refresh_if_stale)
         self._bplan = None  # EDS-biased model replayed as one kernel (see _maybe_install_plan)
         self._tplan = None  # a training step replayed without calling compute() (see _maybe_install_train_plan)
         self._train_seen = None
@@ -212,11 +213,41 @@ class tfcompute:
         """A weight whose value was folded into the plan's generated kernel (simmodel.PairExpr._with) has been written since."""
         return any(t._version != v for t, v in getattr(self, "_plan_folded", ()))
 
+    def pre_replay(self):
+        """Simulation._run_graphed, before it captures or replays: weights written since the last step are copied into the
+        vectors the kernels read at launch -- here, not inside the capture (no copy is recorded) and not only in compute(),
+        which a replayed step never calls."""
+        if self._plan is not None and self._plan_weights is not None:
+            self._plan_weights.refresh_if_stale()
+
+    def _drop_optimizer_state(self):
+        """Forget everything built from the model's compiled optimizer: its descriptor, its torch twin, its moments and the
+        replayed training step (model.compile() with another optimizer, or attach())."""
+        self._tplan = None
+        self._opt_desc = None
+        self._torch_opt = None
+        self._opt_state = None
+        self._compiled_seen = (getattr(self.model, "_compiled", 0), self.model.optimizer)
+
+    def _tplan_current(self):
+        """The replayed training step still is the step the user asks for: training on, nothing to save, the layer it
+        trains still one of the model's."""
+        if not self.train or self.save_output_period:
+            return False
+        layer = self._tplan["layer"]
+        if isinstance(layer, simmodel.TracedWeights):
+            params = self.model.parameters()
+            return all(any(t is p for p in params) for t, _ in layer.elements)
+        return any(v is layer for v in vars(self.model).values())
+
     def graph_key(self):
         # the potential object AND its handle / parameter version (a refresh re-images device weights in place: same handle,
-        # same addresses -- kernels resolve them at launch; a new Potential is a new handle), the context, the output arrays
+        # same addresses -- kernels resolve them at launch; a new Potential is a new handle), the context, the output arrays; and the
+        # number of plan installs: a step that re-traced (set_weights) re-captures -- a cycle captured before the re-trace and
+        # replayed after it did not always give the stepwise loop's bits (tests/test_gpu_plan_state.py)
         p = self._plan
-        return (id(p), getattr(getattr(p, "handle", None), "value", None), getattr(p, "version", 0), id(self.cpp_force),
+        return (id(p), getattr(getattr(p, "handle", None), "value", None), getattr(p, "version", 0), getattr(self, "_plan_installs", 0),
+                id(self.cpp_force),
                 self.force.data_ptr(), self.virial.data_ptr(), int(self.fused), int(self.nneighbor_cutoff), float(self.r_cut))
 
     def compute(self, timestep):
@@ -236,9 +267,11 @@ class tfcompute:
         if self._plan is not None and self._plan_is_stale():
             self._plan = self.model._plan = None      # (re-traced below with the weights' present values)
             self._plan_folded = ()
-        if self._plan is not None and getattr(self, "_plan_weights", None) is not None:
+        if self._plan is not None and self._plan_weights is not None:
             self._plan_weights.refresh_if_stale()     # (weights that are kernel ARGUMENTS: a 4-byte copy each, the plan stays)
-        if self._plan is not None and self.model._plan is self._plan:
+        if self.train and self._compiled_seen != (getattr(self.model, "_compiled", 0), self.model.optimizer):
+            self._drop_optimizer_state()              # (recompiled: the next step is traced and trains with the new optimizer)
+        if self._plan is not None and self.model._plan is self._plan and not self.train:
             self._calls += 1
             # interior rows while the ghost halo is in flight, boundary rows after it
             self.cpp_force.compute_forces_overlapped(timestep, self._arrays(), domain)
@@ -253,11 +286,11 @@ class tfcompute:
             return
         if domain is not None:
             domain.exchange_end()
-        if self._bplan is not None and self.model._plan is self._bplan:
+        if self._bplan is not None and self.model._plan is self._bplan and not self.train:
             self._calls += 1
             self._run_biased_plan()
             return
-        if self._tplan is not None:
+        if self._tplan is not None and self._tplan_current():
             self._calls += 1
             self._run_train_plan()
             return
@@ -265,6 +298,8 @@ class tfcompute:
         bs = s.N if self.batch_size == 0 else self.batch_size
         simmodel._trace_log().clear()
         if self.train:
+            if getattr(self.model, "loss", None) is None:
+                raise ValueError('SimModel has not been compiled')
             self._stage_labels()
         nbatch = 0
         for i in range(s.N // bs + 1):
@@ -448,6 +483,7 @@ class tfcompute:
             self._plan_weights = lay if hasattr(lay, "refresh_if_stale") else None
             self.model._plan = self._plan
             self.cpp_force.set_potential(self._plan)
+            self._plan_installs = getattr(self, "_plan_installs", 0) + 1
             # an energy of several row terms (simmodel._row_forces): the further terms from the tensor the step's kernel wrote
             self._post_ops = post + [self._accumulate_term(p_, typed) for p_, typed in (fused[0].get("extra_potentials") or ())]
         else:

@@ -5,7 +5,8 @@ Mirrors the reference's Python surface for that path (``hoomd.htf``): ``SimModel
 ``RBFExpansion``, ``WCARepulsion``, ``EDSLayer`` ...  All arithmetic runs in the
 hand-written HIP kernels of ``libhtf_amd.so`` (C ABI: include/htf_amd.h; the coarse-grained mapping ops
 ``center_of_mass`` / ``compute_nlist``: include/htf_cg.h; the molecular geometry ops ``mol_bond_distance`` / ``mol_angle`` /
-``mol_dihedral``: include/htf_geom.h).
+``mol_dihedral``: include/htf_geom.h; the cell-binned route of ``compute_nlist``: include/htf_nlist.h).  The offline path
+``iter_from_trajectory`` / ``ArrayTrajectory`` runs a ``SimModel`` over stored frames.
 """
 from . import _lib
 from ._lib import NlistOverflowError, SkewedBoxError
@@ -22,5 +23,6 @@ from . import optimizers
 from .cgmap import sparse_mapping, center_of_mass, compute_nlist
 from .molgeom import mol_bond_distance, mol_angle, mol_dihedral, mol_features_multiple
 from .tensorflowcompute import tfcompute
+from .trajectory import ArrayTrajectory, iter_from_trajectory
 
 __version__ = "0.1.0"

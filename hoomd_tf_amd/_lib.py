@@ -258,6 +258,12 @@ GEOM_PROTOTYPES = {
     "htf_geom_cg_backward": (_i, [_vp, _u, _u, _u, _u, _vp, _vp, _vp, _vp, _vp, _u, _vp, _vp, _vp]),
 }
 
+# the cell-binned route of compute_nlist (include/htf_nlist.h; hoomd_tf_amd/cgmap.py)
+NLIST_PROTOTYPES = {
+    "htf_nlist_cells_scratch_words": (C.c_ulonglong, [_u, _u]),
+    "htf_nlist_cells_forward": (_i, [_vp, _u, _u, _vp, C.c_float, _u, _u, _u, _u, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+}
+
 
 ABI_VERSION = 4  # include/htf_amd.h HTF_AMD_ABI_VERSION: the struct layouts the ctypes Structures of this file mirror
 
@@ -269,7 +275,7 @@ def _load():
             "or `make -C hoomd_tf_amd/csrc`. There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(PROTOTYPES.items()) + list(STANDIN_PROTOTYPES.items()) + list(CG_PROTOTYPES.items())
-                              + list(GEOM_PROTOTYPES.items())):
+                              + list(GEOM_PROTOTYPES.items()) + list(NLIST_PROTOTYPES.items())):
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -314,7 +320,7 @@ class _PybindLib:
     def __init__(self, mod):
         self._mod = mod
         for name, (res, args) in (list(PROTOTYPES.items()) + list(STANDIN_PROTOTYPES.items()) + list(CG_PROTOTYPES.items())
-                                  + list(GEOM_PROTOTYPES.items())):
+                                  + list(GEOM_PROTOTYPES.items()) + list(NLIST_PROTOTYPES.items())):
             fn = getattr(mod, name)  # AttributeError if the module lacks a declared symbol
             ptr_at = tuple(i for i, t in enumerate(args) if _is_pointer(t))
             setattr(self, name, self._wrap(fn, ptr_at, res is _vp))

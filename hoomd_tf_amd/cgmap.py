@@ -3,8 +3,10 @@
 ``sparse_mapping`` builds the B x N bead-from-atom operator once, on the host.  ``center_of_mass`` and
 ``compute_nlist`` are per-step model ops (examples 02, 07, 09 call them inside ``SimModel.compute``): both run in the
 HIP kernels of ``csrc/cg_map.hip`` (C ABI: include/htf_cg.h) and both are differentiable, so a coarse-grained energy
-gives atom forces through ``compute_positions_forces``.  Models that call them step on the eager path.
+gives atom forces through ``compute_positions_forces``.  Models that call them step on the eager path.  Large neighbor
+lists take the cell-binned search of ``csrc/nlist_cells.hip`` (include/htf_nlist.h), which returns the same bits.
 """
+import math
 import weakref
 
 import numpy as np
@@ -127,6 +129,15 @@ def _box_tensor(box_size, device):
     return _BOXES[k]
 
 
+def _box_host(box_size, L):
+    """The three fp32 box lengths of ``_box_tensor(box_size)`` (= ``L``) on the host: read back only when the box was given
+    as a device tensor."""
+    b = _unwrap(box_size)
+    if isinstance(b, torch.Tensor) and b.is_cuda:
+        return L.cpu().tolist()
+    return [float(v) for v in np.asarray(b.cpu().numpy() if isinstance(b, torch.Tensor) else b, dtype=np.float32).reshape(-1)[:3]]
+
+
 def _sorting_enabled():
     sim = standin.current_simulation()
     if sim is None:
@@ -199,15 +210,64 @@ def center_of_mass(positions, mapping, box_size):
 
 
 # ---------------------------------------------------------------------------------------------- neighbor list
+# Smallest M that takes the cell route: the smallest size of tools/nlist_probe.py's table at which it beat all-pairs on the
+# MI355X (8 192: 0.09 ms against 0.16 ms; at 1 024 it lost, 0.09 ms against 0.02 ms).  DESIGN.md §0.3.
+NLIST_CELLS_MIN_M = 8192
+# Cell width >= r_cut + 2^-14 (L + r_cut) per dimension: the margin the exactness argument of csrc/nlist_cells.hip needs.
+_CELL_MARGIN = 2.0 ** -14
+
+
+def _cell_grid(M, L, r_cut):
+    """(nx, ny, nz) of the cell route for ``M`` particles in the box ``L`` (three fp32 values) at cutoff ``r_cut`` (fp32),
+    or None where the route does not apply: a dimension fitting fewer than 3 cells (the 27-cell stencil would wrap onto
+    itself), or a cutoff or box that is not finite and positive.  The grid holds at most max(27, M) cells (scratch stays
+    O(M)): the largest dimension is halved until it does, which only widens cells."""
+    r = float(r_cut)
+    if not (math.isfinite(r) and r > 0.0):
+        return None
+    n = []
+    for Lc in (float(v) for v in L):
+        if not (math.isfinite(Lc) and Lc > 0.0):
+            return None
+        w = r + _CELL_MARGIN * (Lc + r)
+        k = int(Lc // w)
+        while k > 0 and Lc / k < w:
+            k -= 1
+        if k < 3:
+            return None
+        n.append(k)
+    cap = max(27, int(M))
+    while n[0] * n[1] * n[2] > cap:
+        a = n.index(max(n))
+        n[a] = max(3, n[a] // 2)
+    return tuple(n)
+
+
+def _nlist_route(M, L, r_cut):
+    """Which search ``compute_nlist`` runs for ``M`` particles, box ``L`` and cutoff ``r_cut``: ``"cells"`` or ``"all-pairs"``.
+    Both return the same bits; the cell route needs M >= NLIST_CELLS_MIN_M and at least 3 cells along every dimension."""
+    L32 = [float(v) for v in np.asarray(L, dtype=np.float32).reshape(-1)[:3]]
+    if int(M) < NLIST_CELLS_MIN_M or _cell_grid(M, L32, np.float32(r_cut)) is None:
+        return "all-pairs"
+    return "cells"
+
+
 class _ComputeNlist(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, L, r_cut, NN, sorted_, return_types, excl):
+    def forward(ctx, x, L, r_cut, NN, sorted_, return_types, excl, grid):
         M = x.shape[0]
         out = torch.empty((M, NN, 4), dtype=torch.float32, device=x.device)
         idx = torch.empty((M, NN), dtype=torch.int32, device=x.device)
-        check(lib.htf_cg_nlist_forward(x.data_ptr(), x.stride(0), M, L.data_ptr(), r_cut, NN, int(sorted_), int(return_types),
-                                       excl.data_ptr() if excl is not None else None, out.data_ptr(), idx.data_ptr(),
-                                       ops._stream(x)))
+        ex = excl.data_ptr() if excl is not None else None
+        if grid is None:
+            check(lib.htf_cg_nlist_forward(x.data_ptr(), x.stride(0), M, L.data_ptr(), r_cut, NN, int(sorted_), int(return_types),
+                                           ex, out.data_ptr(), idx.data_ptr(), ops._stream(x)))
+        else:
+            nx, ny, nz = grid
+            scratch = torch.empty(int(lib.htf_nlist_cells_scratch_words(M, nx * ny * nz)), dtype=torch.int32, device=x.device)
+            check(lib.htf_nlist_cells_forward(x.data_ptr(), x.stride(0), M, L.data_ptr(), r_cut, nx, ny, nz, NN, int(sorted_),
+                                              int(return_types), ex, scratch.data_ptr(), out.data_ptr(), idx.data_ptr(),
+                                              ops._stream(x)))
         ctx.save_for_backward(idx)
         ctx.cols = x.shape[1]
         return out
@@ -222,7 +282,7 @@ class _ComputeNlist(torch.autograd.Function):
         check(lib.htf_cg_nlist_backward(idx.data_ptr(), M, NN, g.data_ptr(), g3.data_ptr(), ops._stream(idx)))
         if g3 is not gx:
             gx[:, :3] = g3
-        return gx, None, None, None, None, None, None
+        return gx, None, None, None, None, None, None, None
 
 
 def compute_nlist(positions, r_cut, NN, box_size, sorted=False, return_types=False, exclusion_matrix=None):
@@ -233,7 +293,9 @@ def compute_nlist(positions, r_cut, NN, box_size, sorted=False, return_types=Fal
     nearest first; ``sorted=False``: the reference's top_k of the distances, i.e. the NN farthest in range, farthest first.
     Ties go to the lower index.  Column 3: the neighbor's index, or its type (``positions[:, 3]``) with
     ``return_types=True``.  Empty slots are zeros.  Differentiable with respect to the xyz of ``positions``.
-    The cost grows as M^2 (no cell search)."""
+    From NLIST_CELLS_MIN_M particles on, with at least 3 cells of width > r_cut along every dimension, the list is found by
+    a cell-binned search (cost ~ M); otherwise all pairs are tested (cost ~ M^2).  Both give the same bits
+    (``_nlist_route``).  A box given as a device tensor is then read back once, to choose the grid."""
     p = _positions(positions, "positions")
     if return_types and p.shape[1] == 3:
         raise ValueError('Cannot return type if positions does not have type. Make sure positions is N x 4')
@@ -252,5 +314,9 @@ def compute_nlist(positions, r_cut, NN, box_size, sorted=False, return_types=Fal
         if tuple(e.shape) != (M, M):
             raise ValueError("exclusion_matrix must be [%d, %d], got %s" % (M, M, tuple(e.shape)))
         excl = (e != 0).to(device=x.device, dtype=torch.uint8).contiguous()
+    r32 = float(np.float32(float(r_cut)))
+    grid = None
+    if M >= NLIST_CELLS_MIN_M:
+        grid = _cell_grid(M, _box_host(box_size, L), r32)
     _trace_log().append({"op": "compute_nlist"})    # (no replay: a model calling it keeps the eager path)
-    return _ComputeNlist.apply(x, L, float(np.float32(float(r_cut))), NN, bool(sorted), bool(return_types), excl)
+    return _ComputeNlist.apply(x, L, r32, NN, bool(sorted), bool(return_types), excl, grid)

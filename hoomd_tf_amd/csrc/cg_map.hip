@@ -8,12 +8,13 @@
 // is the native ~1-ulp square root, which orders two neighbors whose distances differ by one ulp the wrong way round.)
 #include "htf_common.h"
 #include "htf_cg.h"
+#include "nlist_select.h"
 
 namespace {
 
 constexpr float kTwoPi = 6.28318530717958647692f;
 constexpr float kPi = 3.14159265358979323846f;
-constexpr unsigned long long kEmpty = ~0ull;
+using htf_nlist::kEmpty;
 
 // ------------------------------------------------------------------------------------------------ centre of mass
 // G lanes per bead walk its CSR row; the sums meet by butterfly shuffles inside the lane group.
@@ -95,27 +96,12 @@ __global__ __launch_bounds__(256) void com_backward_kernel(const float *__restri
 }
 
 // ------------------------------------------------------------------------------------------------ neighbor list
-// One wave per row i streams all M candidates through an LDS tile the workgroup's four waves share.  The row's best NN
-// candidates are kept as sorted 64-bit keys in registers (slot s = k * 64 + lane, K = ceil(NN / 64) per lane):
-//   high word: the distance's bits (sorted: nearest first) or their complement (unsorted: farthest first), low word: j,
-// so "smaller key" is exactly the oracle's stable order and every key is distinct.  A candidate below the current worst
-// key is inserted with one ballot (its rank) and one shift of the list by a lane.
+// One wave per row i streams all M candidates through an LDS tile the workgroup's four waves share; the row's list and its
+// insertion step are nlist_select.h's (shared with the cell-binned search of nlist_cells.hip).
 constexpr unsigned kTile = 256;
 
-struct Pair {
-    float x, y, z, d;
-};
-
-__device__ __forceinline__ float min_image(float d, float L) { return __fsub_rn(d, __fmul_rn(rintf(__fdiv_rn(d, L)), L)); }
-
-__device__ __forceinline__ Pair pair_of(float xi, float yi, float zi, float xj, float yj, float zj, float Lx, float Ly, float Lz) {
-    Pair p;
-    p.x = min_image(__fsub_rn(xj, xi), Lx);
-    p.y = min_image(__fsub_rn(yj, yi), Ly);
-    p.z = min_image(__fsub_rn(zj, zi), Lz);
-    p.d = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(p.x, p.x), __fmul_rn(p.y, p.y)), __fmul_rn(p.z, p.z)));
-    return p;
-}
+using htf_nlist::Pair;
+using htf_nlist::pair_of;
 
 template <int K>
 __global__ __launch_bounds__(256) void nlist_forward_kernel(const float *__restrict__ pos, unsigned stride, unsigned M,
@@ -155,58 +141,12 @@ __global__ __launch_bounds__(256) void nlist_forward_kernel(const float *__restr
         for (unsigned sub = 0; sub < n_tile; sub += 64u) {
             const unsigned t = sub + lane, j = base + t;
             unsigned long long cand = kEmpty;
-            if (t < n_tile) {
-                const Pair p = pair_of(xi, yi, zi, tx[t], ty[t], tz[t], Lx, Ly, Lz);
-                bool ok = p.d <= r_cut && p.d >= 5e-4f;
-                if (ok && excl) ok = !excl[(size_t)i * M + j] && !excl[(size_t)j * M + i];
-                if (ok) {
-                    const unsigned bits = __float_as_uint(p.d);
-                    cand = ((unsigned long long)(sorted ? bits : ~bits) << 32) | j;
-                }
-            }
-            unsigned long long pending = __ballot(cand < worst);
-            while (pending) {
-                const int src = __builtin_ctzll(pending);
-                pending &= pending - 1ull;
-                const unsigned long long nk = __shfl(cand, src);
-                if (!(nk < worst)) continue; // (wave-uniform: the list moved since the ballot)
-                unsigned rank = 0;
-#pragma unroll
-                for (int k = 0; k < K; ++k) rank += (unsigned)__popcll(__ballot(key[k] < nk));
-                // shift slots >= rank up by one, nk into slot rank; the highest slot k reads lane 63 of slot k - 1 (not yet moved)
-#pragma unroll
-                for (int k = K - 1; k >= 0; --k) {
-                    unsigned long long up = __shfl_up(key[k], 1u);
-                    const unsigned long long carry = k > 0 ? __shfl(key[k > 0 ? k - 1 : 0], 63) : kEmpty;
-                    if (lane == 0) up = carry;
-                    const unsigned s = (unsigned)k * 64u + lane;
-                    key[k] = s < rank ? key[k] : (s == rank ? nk : up);
-                    if (s >= NN) key[k] = kEmpty;
-                }
-#pragma unroll
-                for (int k = 0; k < K; ++k)
-                    if ((unsigned)k == last_k) worst = __shfl(key[k], (int)last_lane);
-            }
+            if (t < n_tile) cand = htf_nlist::key_of(pair_of(xi, yi, zi, tx[t], ty[t], tz[t], Lx, Ly, Lz), r_cut, sorted, excl, i, j, M);
+            htf_nlist::offer<K>(key, worst, cand, lane, NN, last_k, last_lane);
         }
     }
     if (!row_ok) return;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const unsigned s = (unsigned)k * 64u + lane;
-        if (s >= NN) continue;
-        const size_t o = (size_t)i * NN + s;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        int jj = -1;
-        if (key[k] != kEmpty) {
-            const unsigned j = (unsigned)(key[k] & 0xffffffffull);
-            const Pair p = pair_of(xi, yi, zi, pos[(size_t)j * stride + 0], pos[(size_t)j * stride + 1], pos[(size_t)j * stride + 2],
-                                   Lx, Ly, Lz);
-            v = make_float4(p.x, p.y, p.z, return_types ? pos[(size_t)j * stride + 3] : (float)j);
-            jj = (int)j;
-        }
-        reinterpret_cast<float4 *>(out)[o] = v;
-        out_idx[o] = jj;
-    }
+    htf_nlist::write_row<K>(key, lane, i, NN, pos, stride, xi, yi, zi, Lx, Ly, Lz, return_types, out, out_idx);
 }
 
 __global__ __launch_bounds__(256) void nlist_backward_kernel(const int *__restrict__ idx, unsigned M, unsigned NN,

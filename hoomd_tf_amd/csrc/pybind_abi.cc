@@ -16,6 +16,7 @@
 #include "htf_standin.h"
 #include "htf_cg.h"
 #include "htf_geom.h"
+#include "htf_nlist.h"
 
 namespace py = pybind11;
 
@@ -170,6 +171,11 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
     X(htf_geom_cg_forward) \
     X(htf_geom_cg_backward)
 
+// include/htf_nlist.h: the cell-binned route of compute_nlist (_lib.NLIST_PROTOTYPES)
+#define HTF_NLIST_FUNCTIONS(X) \
+    X(htf_nlist_cells_scratch_words) \
+    X(htf_nlist_cells_forward)
+
 PYBIND11_MODULE(_htf_abi, m) {
     m.doc() = "pybind11 binding of libhtf_amd.so's C ABI: pointers as integers";
     // a stale module (or library): this module's templates were instantiated from one header, the library it resolved at load
@@ -182,5 +188,6 @@ PYBIND11_MODULE(_htf_abi, m) {
     HTF_ABI_FUNCTIONS(X)
     HTF_CG_FUNCTIONS(X)
     HTF_GEOM_FUNCTIONS(X)
+    HTF_NLIST_FUNCTIONS(X)
 #undef X
 }

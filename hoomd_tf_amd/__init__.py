@@ -5,8 +5,9 @@ Mirrors the reference's Python surface for that path (``hoomd.htf``): ``SimModel
 ``RBFExpansion``, ``WCARepulsion``, ``EDSLayer`` ...  All arithmetic runs in the
 hand-written HIP kernels of ``libhtf_amd.so`` (C ABI: include/htf_amd.h; the coarse-grained mapping ops
 ``center_of_mass`` / ``compute_nlist``: include/htf_cg.h; the molecular geometry ops ``mol_bond_distance`` / ``mol_angle`` /
-``mol_dihedral``: include/htf_geom.h; the cell-binned route of ``compute_nlist``: include/htf_nlist.h).  The offline path
-``iter_from_trajectory`` / ``ArrayTrajectory`` runs a ``SimModel`` over stored frames.
+``mol_dihedral``: include/htf_geom.h; the cell-binned route of ``compute_nlist``: include/htf_nlist.h; the descriptor
+network ``DescriptorMLP``: include/htf_desc.h).  The offline path ``iter_from_trajectory`` / ``ArrayTrajectory`` runs a
+``SimModel`` over stored frames.
 """
 from . import _lib
 from ._lib import NlistOverflowError, SkewedBoxError
@@ -18,7 +19,7 @@ from .simmodel import (SimModel, compute_nlist_forces, compute_positions_forces,
                        norm, cast, divide_no_nan, Positions, sort, exp, log, tanh, sqrt, square, pow, abs, minimum, maximum, where,
                        gather, equal, not_equal, erf, erfc, sigmoid, softplus, sin, cos,
                        MolSimModel, find_molecules, MeanTensor)
-from .layers import RBFExpansion, WCARepulsion, EDSLayer, PairMLP, SoftRDFCV, LJLayer, Dense
+from .layers import RBFExpansion, WCARepulsion, EDSLayer, PairMLP, SoftRDFCV, LJLayer, Dense, DescriptorMLP
 from . import optimizers
 from .cgmap import sparse_mapping, center_of_mass, compute_nlist
 from .molgeom import mol_bond_distance, mol_angle, mol_dihedral, mol_features_multiple

@@ -264,6 +264,12 @@ NLIST_PROTOTYPES = {
     "htf_nlist_cells_forward": (_i, [_vp, _u, _u, _vp, C.c_float, _u, _u, _u, _u, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# the descriptor network (include/htf_desc.h; hoomd_tf_amd/layers.py DescriptorMLP)
+DESC_PROTOTYPES = {
+    "htf_desc_forces": (_i, [_vp, _i, _u, _u, _u, _u, _u, _u, _i, _vp, _vp, C.c_float, _vp, _i, _vp, _vp]),
+    "htf_desc_descriptor": (_i, [_vp, _i, _u, _u, _u, _u, _vp, C.c_float, _vp, _i, _vp]),
+}
+
 
 ABI_VERSION = 4  # include/htf_amd.h HTF_AMD_ABI_VERSION: the struct layouts the ctypes Structures of this file mirror
 
@@ -275,7 +281,8 @@ def _load():
             "or `make -C hoomd_tf_amd/csrc`. There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(PROTOTYPES.items()) + list(STANDIN_PROTOTYPES.items()) + list(CG_PROTOTYPES.items())
-                              + list(GEOM_PROTOTYPES.items()) + list(NLIST_PROTOTYPES.items())):
+                              + list(GEOM_PROTOTYPES.items()) + list(NLIST_PROTOTYPES.items())
+                              + list(DESC_PROTOTYPES.items())):
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -320,7 +327,8 @@ class _PybindLib:
     def __init__(self, mod):
         self._mod = mod
         for name, (res, args) in (list(PROTOTYPES.items()) + list(STANDIN_PROTOTYPES.items()) + list(CG_PROTOTYPES.items())
-                                  + list(GEOM_PROTOTYPES.items()) + list(NLIST_PROTOTYPES.items())):
+                                  + list(GEOM_PROTOTYPES.items()) + list(NLIST_PROTOTYPES.items())
+                                  + list(DESC_PROTOTYPES.items())):
             fn = getattr(mod, name)  # AttributeError if the module lacks a declared symbol
             ptr_at = tuple(i for i, t in enumerate(args) if _is_pointer(t))
             setattr(self, name, self._wrap(fn, ptr_at, res is _vp))

@@ -17,6 +17,7 @@
 #include "htf_cg.h"
 #include "htf_geom.h"
 #include "htf_nlist.h"
+#include "htf_desc.h"
 
 namespace py = pybind11;
 
@@ -176,6 +177,11 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
     X(htf_nlist_cells_scratch_words) \
     X(htf_nlist_cells_forward)
 
+// include/htf_desc.h: the descriptor network (_lib.DESC_PROTOTYPES)
+#define HTF_DESC_FUNCTIONS(X) \
+    X(htf_desc_forces) \
+    X(htf_desc_descriptor)
+
 PYBIND11_MODULE(_htf_abi, m) {
     m.doc() = "pybind11 binding of libhtf_amd.so's C ABI: pointers as integers";
     // a stale module (or library): this module's templates were instantiated from one header, the library it resolved at load
@@ -189,5 +195,6 @@ PYBIND11_MODULE(_htf_abi, m) {
     HTF_CG_FUNCTIONS(X)
     HTF_GEOM_FUNCTIONS(X)
     HTF_NLIST_FUNCTIONS(X)
+    HTF_DESC_FUNCTIONS(X)
 #undef X
 }

@@ -1,5 +1,6 @@
 """Counterpart of ``hoomd/htf/layers.py``: RBFExpansion, WCARepulsion, EDSLayer, plus the
-declarative pair-MLP (RBF -> Dense -> Dense -> Dense) that config C3 evaluates on MFMA."""
+declarative pair-MLP (RBF -> Dense -> Dense -> Dense) that config C3 evaluates on MFMA, and the
+per-particle descriptor network DescriptorMLP (RBF channels summed over the neighbors -> Dense stack)."""
 import ctypes as C
 
 import numpy as np
@@ -288,6 +289,124 @@ class PairMLP:
 
     def __call__(self, nlist):
         return simmodel.MLPEnergy(simmodel._as_nlist(nlist), self)
+
+
+class DescriptorMLP:
+    """A descriptor network of Behler-Parrinello / SchNet form, evaluated in one HIP kernel (include/htf_desc.h).
+
+    Called on the neighbor list it returns the symbolic per-particle energy ``E_i``; ``compute_nlist_forces(nlist, E)``
+    gives the forces ``2 sum_j dE_i/dx_ij`` with ``E_i`` in column 3, and the generic route's virial when asked::
+
+        G_i[t*K + k] = sum_j [r_ij > 3e-6] [t_ij = t] exp(-(r_ij - mu_k)^2 / gap)    r_ij = safe_norm(x_ij)
+        E_i = W3^T act(W2^T act(W1^T G_i + b1) + b2) + b3
+
+    ``mu = linspace(low, high, K)`` and ``gap = mu_1 - mu_0`` exactly as RBFExpansion builds them; ``t_ij = rint(nlist[i, j, 3])``
+    when ``n_types > 1`` (a type outside ``[0, n_types)`` contributes nothing), 0 otherwise.  ``activation``: 'tanh' or
+    'linear' for both hidden layers.  The weights (``mlp_params(seed, K=n_types*K, H1, H2)``, Keras order) live in one flat
+    fp32 device tensor ``w`` that the kernel reads at every call: ``set_weights``, ``load_weights`` and in-place writes to
+    ``w`` take effect at the next call.  The energy takes no part in arithmetic with other energies (it raises): evaluate
+    each term with its own ``compute_nlist_forces`` and add the forces.  The layer is not trainable.
+    Limits: ``n_types * K <= 64``, ``H1, H2 <= 64``, at most 256 neighbor slots."""
+
+    name = 'descriptor-mlp'
+    _KEYS = ("W1", "b1", "W2", "b2", "W3", "b3")
+    MAX_D, MAX_H, MAX_NN = 64, 64, 256
+
+    def __init__(self, K=16, H1=32, H2=32, low=0.0, high=3.0, n_types=1, activation="tanh", seed=3, device=None):
+        K, H1, H2, n_types = int(K), int(H1), int(H2), int(n_types)
+        activation = activation or "linear"
+        if activation not in ("tanh", "linear"):
+            raise ValueError("DescriptorMLP: activation must be 'tanh' or 'linear', not %r" % (activation,))
+        if K < 2:
+            raise ValueError("DescriptorMLP: K = %d; the Gaussian width is the spacing of at least two centres" % K)
+        if n_types < 1 or n_types * K > self.MAX_D:
+            raise ValueError("DescriptorMLP: n_types * K = %d * %d channels; the kernel takes 1 to %d" % (n_types, K, self.MAX_D))
+        if not (1 <= H1 <= self.MAX_H and 1 <= H2 <= self.MAX_H):
+            raise ValueError("DescriptorMLP: hidden widths %d, %d outside [1, %d]" % (H1, H2, self.MAX_H))
+        rbf = RBFExpansion(low, high, K)
+        if not rbf.gap > 0:
+            raise ValueError("DescriptorMLP: high = %g must exceed low = %g" % (rbf.high, rbf.low))
+        self.K, self.H1, self.H2, self.n_types, self.activation = K, H1, H2, n_types, activation
+        self.low, self.high, self.centers, self.gap = rbf.low, rbf.high, rbf.centers, rbf.gap
+        self.D = n_types * K
+        if device is None:
+            device = "cuda" if torch.cuda.is_available() else "cpu"
+        p = mlp_params(seed=seed, K=self.D, H1=H1, H2=H2)
+        self._shapes = [p[k].shape for k in self._KEYS]
+        self.w = torch.tensor(np.concatenate([p[k].ravel() for k in self._KEYS]), dtype=torch.float32, device=device)
+        self.mu = torch.tensor(self.centers, dtype=torch.float32, device=device)
+
+    def get_config(self):
+        return {'K': self.K, 'H1': self.H1, 'H2': self.H2, 'low': self.low, 'high': self.high, 'n_types': self.n_types,
+                'activation': self.activation}
+
+    def get_weights(self):
+        flat, out, o = self.w.detach().cpu().numpy(), [], 0
+        for shape in self._shapes:
+            n = int(np.prod(shape))
+            out.append(flat[o:o + n].reshape(shape).copy())
+            o += n
+        return out
+
+    def set_weights(self, ws):
+        ws = list(ws)
+        if len(ws) != len(self._KEYS):
+            raise ValueError("DescriptorMLP: expected %d weight arrays, got %d" % (len(self._KEYS), len(ws)))
+        for k, shape, w in zip(self._KEYS, self._shapes, ws):
+            if np.shape(w) != shape:
+                raise ValueError("DescriptorMLP: shape mismatch for %s: %r, expected %r" % (k, np.shape(w), shape))
+        flat = np.concatenate([np.asarray(w, dtype=np.float32).ravel() for w in ws])
+        with torch.no_grad():
+            self.w.copy_(torch.from_numpy(flat))   # (in place: the next call reads it)
+
+    def save_weights(self, path):
+        np.savez(path, **dict(zip(self._KEYS, self.get_weights())))
+
+    def load_weights(self, path):
+        with np.load(path) as z:
+            self.set_weights([z[k] for k in self._KEYS])
+
+    def _check(self, x, what="nlist"):
+        ops._dev(x, what)
+        if x.dim() != 3 or x.shape[2] != 4:
+            raise ValueError("DescriptorMLP: %s must be [B, NN, 4], got %s" % (what, tuple(x.shape)))
+        ops._dt(x)
+        if x.shape[1] > self.MAX_NN:
+            raise ValueError("DescriptorMLP: NN = %d neighbor slots; the kernel takes at most %d" % (x.shape[1], self.MAX_NN))
+        ops._dev(self.w, "DescriptorMLP.w", torch.float32)
+        if self.w.device != x.device or self.w.numel() != sum(int(np.prod(s)) for s in self._shapes):
+            raise ValueError("DescriptorMLP: the weights (%d floats on %s) do not fit a call on %s" % (self.w.numel(), self.w.device, x.device))
+        return int(x.shape[0]), int(x.shape[1])
+
+    def forces(self, x, virial=False):
+        """The kernel on a pair-vector tensor ``x`` [B, NN, 4] (fp32 or fp64): forces [B, 4] in ``x``'s dtype, and the
+        [B, 3, 3] virial when ``virial``.  compute_nlist_forces calls this for the layer's energy."""
+        B, NN = self._check(x)
+        out = torch.empty((B, 4), dtype=x.dtype, device=x.device)
+        v = torch.empty((B, 3, 3), dtype=x.dtype, device=x.device) if virial else None
+        act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
+        check(lib.htf_desc_forces(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, self.w.data_ptr(),
+                                  self.mu.data_ptr(), float(self.gap), out.data_ptr(), ops._dt(out),
+                                  v.data_ptr() if v is not None else None, ops._stream(x)))
+        return (out, v) if virial else out
+
+    def descriptor(self, nlist):
+        """G [B, D] alone (the kernel's first stage), in the dtype of the pair-vector tensor."""
+        x = simmodel._as_nlist(nlist).tensor
+        B, NN = self._check(x)
+        out = torch.empty((B, self.D), dtype=x.dtype, device=x.device)
+        check(lib.htf_desc_descriptor(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.mu.data_ptr(), float(self.gap),
+                                      out.data_ptr(), ops._dt(out), ops._stream(x)))
+        simmodel._trace_log().append({"op": "descriptor"})   # (no replay: a model calling it keeps the eager path)
+        return out
+
+    def __call__(self, nlist):
+        nl = simmodel._as_nlist(nlist)
+        if len(nl.shape) != 3 or nl.shape[2] != 4:
+            raise ValueError("DescriptorMLP: nlist must be [B, NN, 4], got %s" % (tuple(nl.shape),))
+        if nl.shape[1] > self.MAX_NN:
+            raise ValueError("DescriptorMLP: NN = %d neighbor slots; the kernel takes at most %d" % (nl.shape[1], self.MAX_NN))
+        return simmodel.DescriptorEnergy(nl, self)
 
 
 class EDSLayer:

@@ -1424,6 +1424,32 @@ class MLPEnergy(PairEnergy):
         return self.layer.potential()
 
 
+class DescriptorEnergy(PairEnergy):
+    """DescriptorMLP(nlist): the per-particle energy [N] of the descriptor network.  compute_nlist_forces evaluates it in one
+    kernel (htf_desc_forces) and keeps the step eager.  It does not combine with other energies: arithmetic raises, so a sum
+    the kernel cannot form never reaches the forces."""
+    reduced = True
+
+    def __init__(self, nlist, layer):
+        self.nlist, self.layer = nlist, layer
+
+    def key(self):
+        return ("descriptor-mlp",)
+
+    def potential(self):
+        raise TypeError("DescriptorMLP's energy has no pair potential; pass it to compute_nlist_forces")
+
+    def tensor(self):
+        _trace_log().append({"op": "eager_value"})
+        return self.layer.forces(self.nlist.tensor)[:, 3].clone()
+
+    def _combine(self, *other):
+        raise TypeError("DescriptorMLP's energy cannot be combined with other terms; call compute_nlist_forces on each "
+                        "energy and add the forces")
+
+    __add__ = __radd__ = __sub__ = __rsub__ = __mul__ = __rmul__ = __truediv__ = __rtruediv__ = __pow__ = __neg__ = _combine
+
+
 class SortedRinv:
     """tf.sort(nlist_rinv(nlist), axis=1, direction='DESCENDING'): stays symbolic until sliced."""
 
@@ -1674,6 +1700,13 @@ def compute_nlist_forces(nlist, energy, virial=False):
     if energy.nlist is not nl and energy.nlist.tensor is not nl.tensor:
         raise ValueError('Could not find dependence between energy and nlist.'
                          ' Did you put them in wrong order?')
+    if isinstance(energy, DescriptorEnergy):
+        if getattr(_trace, "training_graph", False):
+            raise NotImplementedError("DescriptorMLP is not trainable: neither tfcompute(train=True) nor train_on_batch "
+                                      "covers a model that holds it")
+        out = energy.layer.forces(nl.tensor, virial)
+        _trace_log().append({"op": "descriptor_mlp"})   # (no plan: a model calling it keeps the eager path)
+        return out
     if isinstance(energy, BiasedEnergy):
         if virial:
             raise ValueError("virial of an EDS-biased energy is not implemented")

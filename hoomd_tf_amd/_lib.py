@@ -94,6 +94,14 @@ class Mirror(C.Structure):
     _fields_ = [("src", C.c_void_p * MIRROR_MAX), ("dst", C.c_void_p * MIRROR_MAX), ("words", C.c_uint * MIRROR_MAX), ("n", C.c_uint)]
 
 
+class Nlist(C.Structure):
+    """htfs_nlist: a stand-in neighbor list between rebuilds -- grid, scratch, outputs (standin.CellNlist fills one)."""
+    _fields_ = [("box", Box), ("r_list", C.c_double), ("ncell3", C.c_int * 3), ("stencil3", C.c_int * 3), ("pitch", C.c_uint),
+                ("type_split", C.c_int)] + [(name, C.c_void_p) for name in (
+                    "cell_of", "scratch", "cell_start", "order", "pos_sorted", "ranges", "n_neigh", "head_list", "nlist", "max_neigh",
+                    "ref", "counter")] + [("image_L", C.c_double * 3)]
+
+
 class BrickWork(C.Structure):
     """htfs_brick_work."""
     _fields_ = [("key", C.c_void_p), ("order", C.c_void_p), ("sort_scratch", C.c_void_p), ("start1", C.c_void_p),
@@ -201,7 +209,6 @@ PROTOTYPES = {
 
 # HOOMD stand-in entry points (include/htf_standin.h) -- outside the drop-in boundary
 STANDIN_PROTOTYPES = {
-    "htfs_gather4": (_i, [_vp, _vp, _vp, _i, _u, _vp]),
     "htfs_gather4_tagged": (_i, [_vp, _vp, _vp, _i, _u, _i, _vp]),
     "htfs_cell_sort": (_i, [_vp, _u, _u, _vp, _vp, _vp, _vp]),
     "htfs_gather4_tagged_live": (_i, [_vp, _vp, _vp, _i, _u, _vp, _i, _vp]),
@@ -229,17 +236,10 @@ STANDIN_PROTOTYPES = {
     "htfs_nve_step": (_i, [_vp, _vp, _vp, _i, _u, _d, C.POINTER(Box), _vp]),
     "htfs_max_displacement2": (_i, [_vp, _vp, _i, _u, C.POINTER(Box), _vp, _vp]),
     "htfs_check_displacement2": (_i, [_vp, _vp, _i, _u, C.POINTER(Box), _vp, _vp, _vp, C.POINTER(Mirror), _vp]),
-    "htfs_build_nlist": (_i, [_vp, _vp, _i, _u, _u, C.POINTER(Box), _d, C.POINTER(_i * 3), C.POINTER(_i * 3), _vp, _u, _i, _vp, _vp, _vp,
-                              _vp, _vp, _vp]),
     "htfs_cell_index": (_i, [_vp, _i, _u, C.POINTER(Box), C.POINTER(_i * 3), _vp, _vp]),
-    "htfs_set_gate": (_i, [_vp, _d]),
-    "htfs_commit_rebuild": (_i, [_vp, _vp, _i, _u, _vp, _vp]),
-    "htfs_rebuild_nlist": (_i, [_vp, _i, _u, C.POINTER(Box), _d, C.POINTER(_i * 3), C.POINTER(_i * 3), _vp, _vp, _vp, _vp, _vp, _u, _i,
-                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "htfs_rebuild_nlist_ghosts": (_i, [_vp, _i, _u, _u, C.POINTER(Box), _d, C.POINTER(_i * 3), C.POINTER(_i * 3), _vp, _vp, _vp, _vp, _vp, _u, _i,
-                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "htfs_check_rebuild_nlist": (_i, [_vp, _i, _u, C.POINTER(Box), _d, C.POINTER(_i * 3), C.POINTER(_i * 3), _vp, _vp, _vp, _vp, _vp, _u, _i,
-                                      _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp]),
+    "htfs_build_nlist": (_i, [C.POINTER(Nlist), _vp, _i, _u, _vp]),
+    "htfs_rebuild_nlist": (_i, [C.POINTER(Nlist), _vp, _i, _u, _u, _i, _vp]),
+    "htfs_check_rebuild_nlist": (_i, [C.POINTER(Nlist), _vp, _i, _u, _u, _i, _vp, _d, _vp, _vp, _vp]),
 }
 
 # coarse-grained mapping ops (include/htf_cg.h): center_of_mass, compute_nlist (hoomd_tf_amd/cgmap.py)
@@ -271,7 +271,7 @@ DESC_PROTOTYPES = {
 }
 
 
-ABI_VERSION = 4  # include/htf_amd.h HTF_AMD_ABI_VERSION: the struct layouts the ctypes Structures of this file mirror
+ABI_VERSION = 5  # include/htf_amd.h HTF_AMD_ABI_VERSION: the struct layouts the ctypes Structures of this file mirror
 
 
 def _load():

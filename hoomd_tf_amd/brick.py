@@ -93,6 +93,8 @@ class BrickDomain:
         self._rebuild_index = 0      # rebuild() calls so far; call i re-plans when i % replan_every == 0
         self._next_light = None      # BrickRun, while capturing: force the kind of the next rebuild (True / False)
         self.n_light = 0
+        self._capturing = False      # BrickRun, inside a hipGraph capture: no host-side waits
+        self._mirrored = False       # BrickRun: the check kernel of a captured cycle carries the counts and flags to the host
         lo, hi = np.asarray(s.box3x3[0], dtype=np.float64), np.asarray(s.box3x3[1], dtype=np.float64)
         self.L = hi - lo
         if self.replica:
@@ -579,7 +581,7 @@ class BrickDomain:
     def rebuild(self):
         """Communicator::migrateParticles + exchangeGhosts: call before every neighbor-list build."""
         s = self.sys
-        capturing = getattr(self, "_capturing", False)   # inside a hipGraph capture (standin.BrickRun): no host-side waits
+        capturing = self._capturing   # inside a hipGraph capture (standin.BrickRun): no host-side waits
         light = self._next_light if self._next_light is not None else (self._rebuild_index % self.replan_every != 0)
         self._rebuild_index += 1
         if light:
@@ -613,7 +615,7 @@ class BrickDomain:
                 self._fill_row_slots()
             for fn in self.after_replan:
                 fn()
-            if not (capturing and getattr(self, "_mirrored", False)):   # (BrickRun: the next check kernel carries them to the host)
+            if not (capturing and self._mirrored):   # (BrickRun: the next check kernel carries them to the host)
                 self._flags_host.copy_(self.counts, non_blocking=True)
             if not capturing:
                 self._flags_event = torch.cuda.Event()
@@ -787,7 +789,7 @@ class BrickDomain:
         inside a hipGraph capture (where the RCCL calls stay on the captured stream)."""
         if self.transport == "peer":
             return True     # stores into the neighbors' inboxes: in flight while the interior rows run, inside a capture too
-        return self.transport != "local" and not getattr(self, "_capturing", False)
+        return self.transport != "local" and not self._capturing
 
     def exchange_begin(self):
         """Post the per-step forward halo: pack the messages from the boundary segment (unless nve_step() has), one grouped
@@ -815,7 +817,7 @@ class BrickDomain:
         # (inside a hipGraph capture the RCCL calls stay on the captured stream: on this ROCm, RCCL enqueued on a stream that
         #  JOINED a capture through an event crashes hipStreamEndCapture -- tools/rccl_graph_probe.py, profiles/r05_rccl_graph_probe.txt)
         self._works = self._exchange(self.halo_send, ghosts, self.ghost_cap, self.ghost_off, TAG_BASE + 16,
-                                     overlap=not getattr(self, "_capturing", False))
+                                     overlap=not self._capturing)
 
     def wait(self):
         """Transport "peer": the receiving half of an exchange (the stream waits on the device; the host does not)."""

@@ -127,14 +127,10 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
     X(htfs_check_displacement2) \
     X(htfs_build_nlist) \
     X(htfs_cell_sort) \
-    X(htfs_gather4) \
     X(htfs_gather4_tagged) \
     X(htfs_gather4_tagged_live) \
     X(htfs_cell_index) \
-    X(htfs_set_gate) \
-    X(htfs_commit_rebuild) \
     X(htfs_rebuild_nlist) \
-    X(htfs_rebuild_nlist_ghosts) \
     X(htfs_check_rebuild_nlist) \
     X(htfs_slab_classify) \
     X(htfs_key_sort16) \

@@ -2,7 +2,6 @@
 // check, binned neighbor search.  Outside the drop-in boundary; exists so the force
 // path can be driven and timed as MD without HOOMD-blue in the image.
 #include <cstdlib>
-#include <unordered_map>
 
 #include "htf_common.h"
 #include "box_math.h"
@@ -11,8 +10,6 @@
 #include "key_sort.h"
 
 namespace htf {
-
-thread_local Gate g_gate = {nullptr, 0.f};
 
 template <typename T>
 __global__ __launch_bounds__(256) void nve_step_kernel(typename Vec4<T>::type *__restrict__ pos,
@@ -520,7 +517,7 @@ namespace htf {
 // depend on the sort but not on each other.  Each of the small kernels of a rebuild costs its launch, the read of the gate and
 // two or three dependent round trips to memory (7-11 us apiece at C3), whatever little it computes.
 // Binning on a grid that is NOT periodic along an axis the caller's coordinates are (a decomposed system's brick + ghost layer,
-// htfs_rebuild_nlist_ghosts' image_L): along such an axis a coordinate is first moved to its image nearest the grid's centre -- a
+// htfs_nlist's image_L): along such an axis a coordinate is first moved to its image nearest the grid's centre -- a
 // row that left the brick through a face on the logical box's boundary has been wrapped to the far side by the integrator, a ghost
 // of such a row arrives a box length away -- for the cell index AND for the sorted copy the search measures plain differences on.
 struct Reimage {
@@ -693,18 +690,13 @@ __global__ __launch_bounds__(256) void cell_order_kernel(const unsigned *__restr
 }
 } // namespace htf
 
-// The first half of a binning scratch (the per-cell counts) is zero on entry: every call that RUNS leaves it so
-// (cell_order_kernel) and a call the gate holds back does not touch it.  A gated call therefore needs no memset -- as long as
-// the last ungated call on this scratch used the same ncell (otherwise the words between the two sizes are stale).
-// Remembered per scratch pointer and calling thread; anything else is zeroed again (an unconditional memset is always right).
-static int zero_counts_if_needed(unsigned *count, unsigned ncell, hipStream_t s) {
-    static thread_local std::unordered_map<const void *, unsigned> zeroed_for;
+// The first half of a binning scratch (the per-cell counts) must be zero on entry.  Every call that RUNS leaves it so
+// (cell_order_kernel) and a call the gate holds back does not touch it, so a caller that knows the last completed call on this
+// scratch used the same ncell may say so (htfs_nlist's scratch_clean) and save the memset; otherwise the words between the two
+// sizes are stale.  The stepwise htfs_cell_sort knows nothing of its caller and always zeroes.
+static int zero_counts(unsigned *count, unsigned ncell, hipStream_t s) {
     HTF_REQUIRE(((uintptr_t)count & 15) == 0, "binning scratch must be 16-byte aligned (cell_scan_kernel reads it with 16-byte loads)");
-    auto it = zeroed_for.find(count);
-    if (!g_gate.disp2 || it == zeroed_for.end() || it->second != ncell) {
-        HTF_CHECK_HIP(hipMemsetAsync(count, 0, (size_t)ncell * sizeof(unsigned), s));
-        zeroed_for[count] = ncell;
-    }
+    HTF_CHECK_HIP(hipMemsetAsync(count, 0, (size_t)ncell * sizeof(unsigned), s));
     return HTF_OK;
 }
 
@@ -715,34 +707,31 @@ extern "C" int htfs_cell_sort(const unsigned *d_cell_of, unsigned Ntot, unsigned
     HTF_REQUIRE(ncell > 0, "htfs_cell_sort: no cells");
     hipStream_t s = (hipStream_t)stream;
     unsigned *count = d_scratch, *cursor = d_scratch + ncell;
-    if (int rc = zero_counts_if_needed(count, ncell, s)) return rc;
-    if (Ntot) hipLaunchKernelGGL(cell_count_kernel, dim3((Ntot + 255) / 256), dim3(256), 0, s, d_cell_of, Ntot, count, g_gate);
-    hipLaunchKernelGGL(cell_scan_kernel, dim3((ncell + kScanChunk - 1) / kScanChunk), dim3(kScanThreads), 0, s, count, ncell, d_cell_start, cursor, g_gate);
-    if (Ntot) hipLaunchKernelGGL(cell_scatter_kernel, dim3((Ntot + 255) / 256), dim3(256), 0, s, d_cell_of, Ntot, cursor, d_order, g_gate);
-    hipLaunchKernelGGL(cell_order_kernel, dim3((ncell + 255) / 256), dim3(256), 0, s, d_cell_start, ncell, d_order, count, g_gate);
+    if (int rc = zero_counts(count, ncell, s)) return rc;
+    if (Ntot) hipLaunchKernelGGL(cell_count_kernel, dim3((Ntot + 255) / 256), dim3(256), 0, s, d_cell_of, Ntot, count, kOpenGate);
+    hipLaunchKernelGGL(cell_scan_kernel, dim3((ncell + kScanChunk - 1) / kScanChunk), dim3(kScanThreads), 0, s, count, ncell, d_cell_start, cursor, kOpenGate);
+    if (Ntot) hipLaunchKernelGGL(cell_scatter_kernel, dim3((Ntot + 255) / 256), dim3(256), 0, s, d_cell_of, Ntot, cursor, d_order, kOpenGate);
+    hipLaunchKernelGGL(cell_order_kernel, dim3((ncell + 255) / 256), dim3(256), 0, s, d_cell_start, ncell, d_order, count, kOpenGate);
     return check_launch("htfs_cell_sort");
 }
 
+// (`tag` is true on every route since the untagged export went; both instantiations stay so that the code object does)
 static int gather4(void *d_dest, const void *d_src, const int *d_order, int dtype, unsigned n, bool tag, int type_split,
                    htf_stream stream, const unsigned *d_n_live = nullptr) {
     using namespace htf;
-    HTF_REQUIRE(d_dest && d_src && d_order, "htfs_gather4: null pointer");
+    HTF_REQUIRE(d_dest && d_src && d_order, "htfs_gather4_tagged: null pointer");
     HTF_REQUIRE(!tag || n <= kTagSide, "htfs_gather4_tagged: %u particles do not fit the 31-bit tag", n);
     if (n == 0) return HTF_OK;
     const dim3 grid((n + 255) / 256), block(256);
     hipStream_t s = (hipStream_t)stream;
     if (dtype == HTF_F32) {
-        if (tag) hipLaunchKernelGGL((gather4_kernel<float4, true>), grid, block, 0, s, (float4 *)d_dest, (const float4 *)d_src, d_order, n, type_split, g_gate, d_n_live);
-        else hipLaunchKernelGGL((gather4_kernel<float4, false>), grid, block, 0, s, (float4 *)d_dest, (const float4 *)d_src, d_order, n, type_split, g_gate, d_n_live);
+        if (tag) hipLaunchKernelGGL((gather4_kernel<float4, true>), grid, block, 0, s, (float4 *)d_dest, (const float4 *)d_src, d_order, n, type_split, kOpenGate, d_n_live);
+        else hipLaunchKernelGGL((gather4_kernel<float4, false>), grid, block, 0, s, (float4 *)d_dest, (const float4 *)d_src, d_order, n, type_split, kOpenGate, d_n_live);
     } else {
-        if (tag) hipLaunchKernelGGL((gather4_kernel<double4, true>), grid, block, 0, s, (double4 *)d_dest, (const double4 *)d_src, d_order, n, type_split, g_gate, d_n_live);
-        else hipLaunchKernelGGL((gather4_kernel<double4, false>), grid, block, 0, s, (double4 *)d_dest, (const double4 *)d_src, d_order, n, type_split, g_gate, d_n_live);
+        if (tag) hipLaunchKernelGGL((gather4_kernel<double4, true>), grid, block, 0, s, (double4 *)d_dest, (const double4 *)d_src, d_order, n, type_split, kOpenGate, d_n_live);
+        else hipLaunchKernelGGL((gather4_kernel<double4, false>), grid, block, 0, s, (double4 *)d_dest, (const double4 *)d_src, d_order, n, type_split, kOpenGate, d_n_live);
     }
     return check_launch("gather4_kernel");
-}
-
-extern "C" int htfs_gather4(void *d_dest, const void *d_src, const int *d_order, int dtype, unsigned n, htf_stream stream) {
-    return gather4(d_dest, d_src, d_order, dtype, n, false, -1, stream);
 }
 
 extern "C" int htfs_gather4_tagged(void *d_dest, const void *d_src, const int *d_order, int dtype, unsigned n, int type_split,
@@ -858,31 +847,32 @@ extern "C" int htfs_cell_index(const void *d_pos, int dtype, unsigned Ntot, cons
     if (Ntot == 0) return HTF_OK;
     unsigned grid = (Ntot + 255) / 256;
     if (dtype == HTF_F32)
-        hipLaunchKernelGGL((cell_index_kernel<float>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float4 *)d_pos, Ntot, make_sbox<float>(box), ncell3[0], ncell3[1], ncell3[2], d_cell_of, g_gate);
+        hipLaunchKernelGGL((cell_index_kernel<float>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float4 *)d_pos, Ntot, make_sbox<float>(box), ncell3[0], ncell3[1], ncell3[2], d_cell_of, kOpenGate);
     else
-        hipLaunchKernelGGL((cell_index_kernel<double>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const double4 *)d_pos, Ntot, make_sbox<double>(box), ncell3[0], ncell3[1], ncell3[2], d_cell_of, g_gate);
+        hipLaunchKernelGGL((cell_index_kernel<double>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const double4 *)d_pos, Ntot, make_sbox<double>(box), ncell3[0], ncell3[1], ncell3[2], d_cell_of, kOpenGate);
     return check_launch("cell_index_kernel");
 }
 
-// what bins_finish_kernel does beside the range table when the search is part of htfs_rebuild_nlist
+// what bins_finish_kernel does beside the range table when the search is part of htfs_rebuild_nlist: the tagged sorted copy of
+// the n binned positions, ref <- pos, counter += 1
 struct FinishArgs {
-    void *pos_sorted;       // <- pos[order], tagged
-    const int *order;
-    unsigned n;             // particles binned
-    void *ref;              // <- pos (nullable)
-    unsigned n_ref;
-    unsigned *counter;      // += 1 (nullable)
+    unsigned n;
     htf::Reimage im;
 };
 
-static int build_nlist_impl(const void *d_pos, const void *d_pos_sorted, int dtype, unsigned N, unsigned Ntot,
-                            const htf_box *box, double r_list, const int *ncell3, const int *stencil3,
-                            const unsigned *d_cell_start, unsigned pitch, int type_split,
-                            unsigned *d_n_neigh, unsigned *d_head_list, unsigned *d_nlist, unsigned *d_max_neigh,
-                            void *d_ranges_v, htf_stream stream, const FinishArgs *fin) {
-    (void)Ntot;
-    HTF_REQUIRE(d_pos && d_pos_sorted && box && ncell3 && stencil3 && d_cell_start && d_n_neigh && d_head_list && d_nlist && d_max_neigh,
+static int build_nlist_impl(const htfs_nlist *l, const void *d_pos, int dtype, unsigned N, htf_stream stream, htf::Gate gate,
+                            const FinishArgs *fin) {
+    using namespace htf;
+    HTF_REQUIRE(l && d_pos && l->pos_sorted && l->cell_start && l->n_neigh && l->head_list && l->nlist && l->max_neigh,
                 "htfs_build_nlist: null pointer");
+    const htf_box *box = &l->box;
+    const int *ncell3 = l->ncell3, *stencil3 = l->stencil3;
+    const unsigned *d_cell_start = l->cell_start;
+    const void *d_pos_sorted = l->pos_sorted;
+    const unsigned pitch = l->pitch;
+    const int type_split = l->type_split;
+    const double r_list = l->r_list;
+    unsigned *d_n_neigh = l->n_neigh, *d_head_list = l->head_list, *d_nlist = l->nlist, *d_max_neigh = l->max_neigh;
     HTF_REQUIRE(pitch > 0, "htfs_build_nlist: pitch must be > 0");
     for (int d = 0; d < 3; ++d) {
         const double w = (box->hi[d] - box->lo[d]) / ncell3[d];
@@ -896,21 +886,21 @@ static int build_nlist_impl(const void *d_pos, const void *d_pos_sorted, int dty
     // this file, freed and re-allocated when a larger grid came along -- under the feet of any hipGraph that had captured it.)
     const unsigned ncell = (unsigned)(ncell3[0] * ncell3[1] * ncell3[2]);
     const unsigned nrow = (unsigned)((2 * stencil3[1] + 1) * (2 * stencil3[2] + 1));
-    HTF_REQUIRE(d_ranges_v && ((uintptr_t)d_ranges_v & 15) == 0, "htfs_build_nlist: d_ranges must be a 16-byte aligned table of 4 * ncell * rows words");
-    uint4 *d_ranges = (uint4 *)d_ranges_v;
+    HTF_REQUIRE(l->ranges && ((uintptr_t)l->ranges & 15) == 0, "htfs_build_nlist: ranges must be a 16-byte aligned table of 4 * ncell * rows words");
+    uint4 *d_ranges = (uint4 *)l->ranges;
     const RangesArgs ra = {ncell3[0], ncell3[1], ncell3[2], stencil3[0], stencil3[1], stencil3[2], (int)box->periodic[0],
                            (int)box->periodic[1], (int)box->periodic[2], d_cell_start, d_ranges, d_max_neigh};
     const unsigned nb_ranges = (ncell * nrow + 255) / 256;
     if (fin == nullptr) {
-        hipLaunchKernelGGL(cell_ranges_kernel, dim3(nb_ranges), dim3(256), 0, (hipStream_t)stream, ra, g_gate);
+        hipLaunchKernelGGL(cell_ranges_kernel, dim3(nb_ranges), dim3(256), 0, (hipStream_t)stream, ra, gate);
     } else {
         const unsigned nb = nb_ranges + (fin->n + 255) / 256 + (fin->n == 0 ? 1u : 0u);
         if (dtype == HTF_F32)
-            hipLaunchKernelGGL((bins_finish_kernel<float4>), dim3(nb), dim3(256), 0, (hipStream_t)stream, ra, nb_ranges, (float4 *)fin->pos_sorted,
-                               (const float4 *)d_pos, fin->order, fin->n, type_split, (float4 *)fin->ref, fin->n_ref, fin->counter, fin->im, g_gate);
+            hipLaunchKernelGGL((bins_finish_kernel<float4>), dim3(nb), dim3(256), 0, (hipStream_t)stream, ra, nb_ranges, (float4 *)l->pos_sorted,
+                               (const float4 *)d_pos, (const int *)l->order, fin->n, type_split, (float4 *)l->ref, N, l->counter, fin->im, gate);
         else
-            hipLaunchKernelGGL((bins_finish_kernel<double4>), dim3(nb), dim3(256), 0, (hipStream_t)stream, ra, nb_ranges, (double4 *)fin->pos_sorted,
-                               (const double4 *)d_pos, fin->order, fin->n, type_split, (double4 *)fin->ref, fin->n_ref, fin->counter, fin->im, g_gate);
+            hipLaunchKernelGGL((bins_finish_kernel<double4>), dim3(nb), dim3(256), 0, (hipStream_t)stream, ra, nb_ranges, (double4 *)l->pos_sorted,
+                               (const double4 *)d_pos, (const int *)l->order, fin->n, type_split, (double4 *)l->ref, N, l->counter, fin->im, gate);
     }
     const bool fine = stencil3[0] == 2 || stencil3[1] == 2 || stencil3[2] == 2; // short ranges: 8-lane groups waste fewer lanes
 #define HTFS_NL(T, V4, G)                                                                                              \
@@ -919,13 +909,13 @@ static int build_nlist_impl(const void *d_pos, const void *d_pos_sorted, int dty
     hipLaunchKernelGGL((build_nlist_kernel<T, G, S>), dim3((N + 4 * (64 / G) - 1) / (4 * (64 / G))), dim3(256), 0, (hipStream_t)stream, \
                        (const V4 *)d_pos, (const V4 *)d_pos_sorted, N, make_sbox<T>(box), (T)(r_list * r_list), ncell3[0],  \
                        ncell3[1], ncell3[2], stencil3[0], stencil3[1], stencil3[2], d_cell_start, pitch,      \
-                       type_split, d_n_neigh, d_head_list, d_nlist, d_max_neigh, (const uint4 *)d_ranges, g_gate)
+                       type_split, d_n_neigh, d_head_list, d_nlist, d_max_neigh, (const uint4 *)d_ranges, gate)
 #define HTFS_NLC(T, V4)                                                                                                \
     if (shift) HTFS_NLC_(T, V4, true); else HTFS_NLC_(T, V4, false)
 #define HTFS_NLC_(T, V4, S)                                                                                            \
     hipLaunchKernelGGL((build_nlist_cells_kernel<T, S>), dim3((ncell * cell_split + 3) / 4), dim3(256), 0, (hipStream_t)stream, \
                        (const V4 *)d_pos_sorted, N, make_sbox<T>(box), (T)(r_list * r_list), ncell, (int)nrow, d_cell_start, pitch, \
-                       type_split, d_n_neigh, d_head_list, d_nlist, d_max_neigh, (const uint4 *)d_ranges, cell_split, g_gate)
+                       type_split, d_n_neigh, d_head_list, d_nlist, d_max_neigh, (const uint4 *)d_ranges, cell_split, gate)
     // with >= 7 cells along every periodic axis a stencil (<= 2 cells each way, plus a particle's place inside its own cell)
     // never reaches half a box length: the near image of a candidate follows from its cell alone
     bool shift = true;
@@ -956,127 +946,70 @@ static int build_nlist_impl(const void *d_pos, const void *d_pos_sorted, int dty
     return check_launch("build_nlist_kernel");
 }
 
-extern "C" int htfs_build_nlist(const void *d_pos, const void *d_pos_sorted, int dtype, unsigned N, unsigned Ntot,
-                                const htf_box *box, double r_list, const int *ncell3, const int *stencil3,
-                                const unsigned *d_cell_start, unsigned pitch, int type_split,
-                                unsigned *d_n_neigh, unsigned *d_head_list, unsigned *d_nlist, unsigned *d_max_neigh,
-                                void *d_ranges, htf_stream stream) {
-    return build_nlist_impl(d_pos, d_pos_sorted, dtype, N, Ntot, box, r_list, ncell3, stencil3, d_cell_start, pitch, type_split, d_n_neigh,
-                            d_head_list, d_nlist, d_max_neigh, d_ranges, stream, nullptr);
+extern "C" int htfs_build_nlist(const htfs_nlist *nl, const void *d_pos, int dtype, unsigned N, htf_stream stream) {
+    return build_nlist_impl(nl, d_pos, dtype, N, stream, htf::kOpenGate, nullptr);
 }
 
-// The whole rebuild of a single-domain list -- htfs_cell_index, htfs_cell_sort, htfs_gather4_tagged, htfs_build_nlist and
-// htfs_commit_rebuild on the same arguments -- in six launches instead of nine (index + count in one kernel; range table,
-// sorted copy and commit in one): the small kernels are launch- and latency-bound, and a gated rebuild pays for every one of
-// them even when the gate is closed.
-static int rebuild_nlist_impl(const void *d_pos, int dtype, unsigned N, unsigned Ntot, const htf_box *box, double r_list, const int *ncell3,
-                              const int *stencil3, unsigned *d_cell_of, unsigned *d_scratch, unsigned *d_cell_start,
-                              unsigned *d_order, void *d_pos_sorted, unsigned pitch, int type_split, unsigned *d_n_neigh,
-                              unsigned *d_head_list, unsigned *d_nlist, unsigned *d_max_neigh, void *d_ref,
-                              unsigned *d_counter, void *d_ranges, htf_stream stream, bool scratch_clean = false,
-                              const double *image_L = nullptr) {
+// The whole rebuild -- htfs_cell_index, htfs_cell_sort, htfs_gather4_tagged, htfs_build_nlist and the commit of the reference
+// positions -- in six launches instead of nine (index + count in one kernel; range table, sorted copy and commit in one): the
+// small kernels are launch- and latency-bound, and a gated rebuild pays for every one of them even when the gate is closed.
+// Candidates may include ghosts behind the N local rows (and inert rows anywhere: a decomposed system's fixed-capacity arrays):
+// Ntot positions binned, N rows searched and committed.
+static int rebuild_nlist_impl(const htfs_nlist *l, const void *d_pos, int dtype, unsigned N, unsigned Ntot, bool scratch_clean,
+                              htf_stream stream, htf::Gate gate) {
     using namespace htf;
-    HTF_REQUIRE(d_pos && box && ncell3 && stencil3 && d_cell_of && d_scratch && d_cell_start && d_order && d_pos_sorted,
-                "htfs_rebuild_nlist: null pointer");
+    HTF_REQUIRE(l && d_pos && l->cell_of && l->scratch && l->cell_start && l->order && l->pos_sorted, "htfs_rebuild_nlist: null pointer");
     HTF_REQUIRE(Ntot >= N, "htfs_rebuild_nlist: Ntot %u < N %u", Ntot, N);
     if (N == 0) return HTF_OK;
+    const htf_box *box = &l->box;
+    const int *ncell3 = l->ncell3;
     const unsigned ncell = (unsigned)(ncell3[0] * ncell3[1] * ncell3[2]);
     HTF_REQUIRE(ncell > 0, "htfs_rebuild_nlist: no cells");
     hipStream_t s = (hipStream_t)stream;
-    unsigned *count = d_scratch, *cursor = d_scratch + ncell;
+    unsigned *count = l->scratch, *cursor = l->scratch + ncell;
     if (!scratch_clean)
-        if (int rc = zero_counts_if_needed(count, ncell, s)) return rc; // (as htfs_cell_sort)
+        if (int rc = zero_counts(count, ncell, s)) return rc;
     const unsigned grid = (Ntot + 255) / 256;
     Reimage im = {};
     for (int d = 0; d < 3; ++d) {
-        im.L[d] = image_L != nullptr && !box->periodic[d] ? image_L[d] : 0.0;
+        im.L[d] = !box->periodic[d] ? l->image_L[d] : 0.0;
         im.c[d] = 0.5 * (box->lo[d] + box->hi[d]);
-        HTF_REQUIRE(im.L[d] == 0.0 || im.L[d] >= box->hi[d] - box->lo[d], "htfs_rebuild_nlist_ghosts: image length %g along axis %d is shorter than the grid", im.L[d], d);
+        HTF_REQUIRE(im.L[d] == 0.0 || im.L[d] >= box->hi[d] - box->lo[d], "htfs_rebuild_nlist: image length %g along axis %d is shorter than the grid", im.L[d], d);
     }
     if (dtype == HTF_F32)
         hipLaunchKernelGGL((cell_index_count_kernel<float>), dim3(grid), dim3(256), 0, s, (const float4 *)d_pos, Ntot, make_sbox<float>(box),
-                           ncell3[0], ncell3[1], ncell3[2], d_cell_of, count, im, g_gate);
+                           ncell3[0], ncell3[1], ncell3[2], l->cell_of, count, im, gate);
     else
         hipLaunchKernelGGL((cell_index_count_kernel<double>), dim3(grid), dim3(256), 0, s, (const double4 *)d_pos, Ntot, make_sbox<double>(box),
-                           ncell3[0], ncell3[1], ncell3[2], d_cell_of, count, im, g_gate);
-    hipLaunchKernelGGL(cell_scan_kernel, dim3((ncell + kScanChunk - 1) / kScanChunk), dim3(kScanThreads), 0, s, count, ncell, d_cell_start, cursor, g_gate);
-    hipLaunchKernelGGL(cell_scatter_kernel, dim3(grid), dim3(256), 0, s, d_cell_of, Ntot, cursor, d_order, g_gate);
-    hipLaunchKernelGGL(cell_order_kernel, dim3((ncell + 255) / 256), dim3(256), 0, s, d_cell_start, ncell, d_order, count, g_gate);
-    const FinishArgs fin = {d_pos_sorted, (const int *)d_order, Ntot, d_ref, N, d_counter, im};
-    return build_nlist_impl(d_pos, d_pos_sorted, dtype, N, Ntot, box, r_list, ncell3, stencil3, d_cell_start, pitch, type_split, d_n_neigh,
-                            d_head_list, d_nlist, d_max_neigh, d_ranges, stream, &fin);
+                           ncell3[0], ncell3[1], ncell3[2], l->cell_of, count, im, gate);
+    hipLaunchKernelGGL(cell_scan_kernel, dim3((ncell + kScanChunk - 1) / kScanChunk), dim3(kScanThreads), 0, s, count, ncell, l->cell_start, cursor, gate);
+    hipLaunchKernelGGL(cell_scatter_kernel, dim3(grid), dim3(256), 0, s, l->cell_of, Ntot, cursor, l->order, gate);
+    hipLaunchKernelGGL(cell_order_kernel, dim3((ncell + 255) / 256), dim3(256), 0, s, l->cell_start, ncell, l->order, count, gate);
+    const FinishArgs fin = {Ntot, im};
+    return build_nlist_impl(l, d_pos, dtype, N, stream, gate, &fin);
 }
 
-extern "C" int htfs_rebuild_nlist(const void *d_pos, int dtype, unsigned N, const htf_box *box, double r_list, const int *ncell3,
-                                  const int *stencil3, unsigned *d_cell_of, unsigned *d_scratch, unsigned *d_cell_start,
-                                  unsigned *d_order, void *d_pos_sorted, unsigned pitch, int type_split, unsigned *d_n_neigh,
-                                  unsigned *d_head_list, unsigned *d_nlist, unsigned *d_max_neigh, void *d_ref,
-                                  unsigned *d_counter, void *d_ranges, htf_stream stream) {
-    return rebuild_nlist_impl(d_pos, dtype, N, N, box, r_list, ncell3, stencil3, d_cell_of, d_scratch, d_cell_start, d_order, d_pos_sorted,
-                              pitch, type_split, d_n_neigh, d_head_list, d_nlist, d_max_neigh, d_ref, d_counter, d_ranges, stream);
-}
-
-// the same for a list whose candidates include ghosts behind the N local rows (and inert rows anywhere: a decomposed system's
-// fixed-capacity arrays): Ntot positions binned, N rows searched and committed -- six launches where the separate calls take ten
-extern "C" int htfs_rebuild_nlist_ghosts(const void *d_pos, int dtype, unsigned N, unsigned Ntot, const htf_box *box, double r_list,
-                                         const int *ncell3, const int *stencil3, unsigned *d_cell_of, unsigned *d_scratch,
-                                         unsigned *d_cell_start, unsigned *d_order, void *d_pos_sorted, unsigned pitch, int type_split,
-                                         unsigned *d_n_neigh, unsigned *d_head_list, unsigned *d_nlist, unsigned *d_max_neigh, void *d_ref,
-                                         unsigned *d_counter, void *d_ranges, int scratch_clean, const double *image_L, htf_stream stream) {
-    return rebuild_nlist_impl(d_pos, dtype, N, Ntot, box, r_list, ncell3, stencil3, d_cell_of, d_scratch, d_cell_start, d_order, d_pos_sorted,
-                              pitch, type_split, d_n_neigh, d_head_list, d_nlist, d_max_neigh, d_ref, d_counter, d_ranges, stream,
-                              scratch_clean != 0, image_L);
+extern "C" int htfs_rebuild_nlist(const htfs_nlist *nl, const void *d_pos, int dtype, unsigned N, unsigned Ntot, int scratch_clean,
+                                  htf_stream stream) {
+    return rebuild_nlist_impl(nl, d_pos, dtype, N, Ntot, scratch_clean != 0, stream, htf::kOpenGate);
 }
 
 // A whole check step of a device-decided list in ONE call (the host's share of a small system's step is its enqueue): the
-// displacement word zeroed and filled, the gate set to it, htfs_rebuild_nlist behind the gate, the gate taken off, and the two
-// status words copied to pinned host memory for the NEXT check to read (nullable).
-extern "C" int htfs_check_rebuild_nlist(const void *d_pos, int dtype, unsigned N, const htf_box *box, double r_list, const int *ncell3,
-                                        const int *stencil3, unsigned *d_cell_of, unsigned *d_scratch, unsigned *d_cell_start,
-                                        unsigned *d_order, void *d_pos_sorted, unsigned pitch, int type_split, unsigned *d_n_neigh,
-                                        unsigned *d_head_list, unsigned *d_nlist, unsigned *d_stat2, void *d_ref, float *d_disp2,
-                                        double threshold2, unsigned *h_stat2, void *d_ranges, htf_stream stream) {
-    HTF_REQUIRE(d_ref && d_disp2 && d_stat2, "htfs_check_rebuild_nlist: null pointer");
+// displacement word zeroed and filled, the rebuild behind a gate on it, and the two status words copied to pinned host memory
+// for the NEXT check to read (nullable).
+extern "C" int htfs_check_rebuild_nlist(const htfs_nlist *nl, const void *d_pos, int dtype, unsigned N, unsigned Ntot, int scratch_clean,
+                                        float *d_disp2, double threshold2, unsigned *d_stat2, unsigned *h_stat2, htf_stream stream) {
+    HTF_REQUIRE(nl && nl->ref && d_disp2 && d_stat2, "htfs_check_rebuild_nlist: null pointer");
     if (N == 0) return HTF_OK;
     HTF_CHECK_HIP(hipMemsetAsync(d_disp2, 0, sizeof(float), (hipStream_t)stream));
-    int rc = htfs_max_displacement2(d_pos, d_ref, dtype, N, box, d_disp2, stream);
+    int rc = htfs_max_displacement2(d_pos, nl->ref, dtype, N, &nl->box, d_disp2, stream);
     if (rc != HTF_OK) return rc;
-    rc = htfs_set_gate(d_disp2, threshold2);
-    if (rc != HTF_OK) return rc;
-    rc = htfs_rebuild_nlist(d_pos, dtype, N, box, r_list, ncell3, stencil3, d_cell_of, d_scratch, d_cell_start, d_order, d_pos_sorted, pitch,
-                            type_split, d_n_neigh, d_head_list, d_nlist, d_stat2, d_ref, d_stat2 + 1, d_ranges, stream);
-    (void)htfs_set_gate(nullptr, 0.0);
+    htfs_nlist l = *nl;
+    l.max_neigh = d_stat2;
+    l.counter = d_stat2 + 1;
+    rc = rebuild_nlist_impl(&l, d_pos, dtype, N, Ntot, scratch_clean != 0, stream, htf::Gate{d_disp2, (float)threshold2});
     if (rc != HTF_OK) return rc;
     if (h_stat2 != nullptr)
         HTF_CHECK_HIP(hipMemcpyAsync(h_stat2, d_stat2, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream));
     return HTF_OK;
-}
-
-namespace htf {
-// the tail of a (conditional) rebuild: reference positions <- current positions, rebuild counter + 1
-template <typename V>
-__global__ __launch_bounds__(256) void commit_rebuild_kernel(V *__restrict__ ref, const V *__restrict__ pos, unsigned n,
-                                                             unsigned *__restrict__ counter, Gate gate) {
-    if (gate.closed()) return;
-    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) ref[i] = pos[i];
-    if (i == 0 && counter != nullptr) *counter += 1u;
-}
-} // namespace htf
-
-extern "C" int htfs_set_gate(const float *d_disp2, double threshold2) {
-    g_gate.disp2 = d_disp2;
-    g_gate.thr2 = (float)threshold2;
-    return HTF_OK;
-}
-
-extern "C" int htfs_commit_rebuild(void *d_ref, const void *d_pos, int dtype, unsigned N, unsigned *d_counter,
-                                   htf_stream stream) {
-    HTF_REQUIRE(d_ref && d_pos, "htfs_commit_rebuild: null pointer");
-    const unsigned grid = (N + 255) / 256 > 0 ? (N + 255) / 256 : 1;
-    if (dtype == HTF_F32)
-        hipLaunchKernelGGL((commit_rebuild_kernel<float4>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (float4 *)d_ref, (const float4 *)d_pos, N, d_counter, g_gate);
-    else
-        hipLaunchKernelGGL((commit_rebuild_kernel<double4>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (double4 *)d_ref, (const double4 *)d_pos, N, d_counter, g_gate);
-    return check_launch("commit_rebuild_kernel");
 }

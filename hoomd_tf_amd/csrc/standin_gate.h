@@ -5,16 +5,16 @@
 
 namespace htf {
 
-// Device-side gate of a conditional neighbor-list rebuild: between htfs_set_gate(d_disp2, thr2) and
-// htfs_set_gate(NULL, 0) every binning / search / migration kernel launched through the stand-in returns at entry
-// unless *d_disp2 > thr2 -- the decision NeighborList::distanceCheck takes on the host is taken by the
-// kernels themselves, so the step loop never waits for a read-back.
+// Device-side gate of a conditional neighbor-list rebuild: every binning / search kernel takes one by value and returns at
+// entry unless it is open or *disp2 > thr2 when the kernel RUNS -- the decision NeighborList::distanceCheck takes on the host
+// is taken by the kernels themselves, so the step loop never waits for a read-back.  htfs_check_rebuild_nlist makes the gate
+// from its arguments and hands it down to every launch; every other entry point passes kOpenGate.
 struct Gate {
     const float *disp2;
     float thr2;
     __device__ __forceinline__ bool closed() const { return disp2 != nullptr && !(*disp2 > thr2); }
 };
-extern thread_local Gate g_gate;
+constexpr Gate kOpenGate = {nullptr, 0.f};
 
 // An INERT row (round 5, hoomd_tf_amd/brick.py): a slot of a fixed-capacity particle array that holds no particle.  Its x is
 // NaN: every distance to it compares false (never a neighbor, never inside a cutoff), the binning leaves it out of every

@@ -137,9 +137,21 @@ class DeferredRebuildRule:
         self.hist = []
 
 
+def _described(name):
+    """A public attribute of CellNlist that is also a field of its htfs_nlist: assigning it, from inside or outside the class,
+    keeps the two in step (a tensor by its address, None as 0)."""
+    def fset(self, v):
+        self.__dict__[name] = v
+        setattr(self._desc, name, v.data_ptr() if torch.is_tensor(v) else int(v or 0))
+    return property(lambda self: self.__dict__[name], fset)
+
+
 class CellNlist:
     """hoomd.md.nlist.cell analogue: FULL neighbor list, fixed pitch head list, rebuilt
     when any particle has moved more than r_buff / 2 (NeighborList::distanceCheck)."""
+
+    pitch, n_neigh, head_list, nlist = (_described(k) for k in ("pitch", "n_neigh", "head_list", "nlist"))
+    type_split = _described("type_split")  # >= 0: no pairs across this type id (mapped beads vs all-atom particles); -1: none
 
     def __init__(self, system, r_cut, r_buff=0.4, pitch=None, check_period=1, sort_particles=False,
                  device_decision=False, deferred_reference=False):
@@ -153,11 +165,10 @@ class CellNlist:
         self._dd_i = 0
         # device_decision: after the first build the distance check and the rebuild it may trigger are
         # enqueued together, the binning / search kernels gated on the device by the check's result
-        # (htfs_set_gate): the step loop never reads the check back.  The buffers keep their addresses, a
+        # (htfs_check_rebuild_nlist): the step loop never reads the check back.  The buffers keep their addresses, a
         # neighbor-row overflow (more entries than ``pitch``) is reported one check late.  Single-rank,
         # unsorted systems only; otherwise the host decides as NeighborList::distanceCheck does.
         self.device_decision = bool(device_decision)
-        self._stat = self._stat_host = self._stat_event = None
         # HOOMD's SFCPackUpdater analogue: renumber the local particles in cell order at every
         # rebuild, so that a particle's neighbors sit in a few contiguous index runs and the
         # position gathers of the force path coalesce.  Off by default (it changes particle
@@ -166,15 +177,30 @@ class CellNlist:
         self.r_cut = float(r_cut)
         self.r_buff = float(r_buff)
         self.check_period = int(check_period)
+        # the list as the C side sees it (include/htf_standin.h htfs_nlist): every rebuild call takes this and nothing else
+        # about the list; filled where a buffer is allocated, and by the attributes above the constructor
+        self._desc = _lib.Nlist()
         self.pitch = pitch
         self.n_neigh = self.head_list = self.nlist = None
+        self.type_split = -1
         self._ref = None
         self._disp = torch.zeros(1, dtype=torch.float32, device=system.device)
         self._max = torch.zeros(1, dtype=torch.int32, device=system.device)
+        self._desc.max_neigh = self._max.data_ptr()
         self.n_builds = 0
         self._subscribers = []
         self.domain = None  # SlabDomain when the box is decomposed over ranks
-        self.type_split = -1  # >= 0: no pairs across this type id (mapped beads vs all-atom particles)
+        self._sbox_key = None       # what _desc.box was made from
+        self._scr_n = None          # (Ntot, ncell, stencil y, stencil z) the scratch buffers are sized for
+        self._grid = None           # (cells per direction, stencil half-widths, ncell) of the last sizing
+        self._scratch_clean = None  # (scratch address, ncell) whose per-cell counts the last completed binning left zero
+        self._step_done = None      # the timestep compute() last ran for
+        self._capturing = False     # set by whoever records a hipGraph around this list's calls: no host-side waits
+        # a rebuild's largest row reaches the host one check late, in pinned memory, with an event behind the copy:
+        # device-decided checks leave [largest row, rebuilds] in _stat, rebuilds without read-back the row alone in _max
+        self._stat = self._stat_host = self._stat_event = None
+        self._max_host = self._max_event = None
+        self._mirrored = False      # BrickRun: the check kernel of a captured cycle carries _max to _max_host
 
     def subscribe(self, rcut_fn):
         """NeighborList r_cut subscription (tensorflowcompute.py:116-120): the list is
@@ -203,18 +229,6 @@ class CellNlist:
                 n[d], w[d] = coarse, 1
         return n, w
 
-    def _image_lengths(self):
-        """The period of the coordinates along the axes the domain's local grid is not periodic on (htfs_rebuild_nlist_ghosts'
-        image_L), or None."""
-        fn = getattr(self.domain, "image_lengths", None)
-        if fn is None:
-            return None
-        key = fn()
-        if getattr(self, "_image_key", None) != key:
-            self._image_key = key
-            self._image_arr = (C.c_double * 3)(*key) if any(key) else None
-        return self._image_arr
-
     def _search_box(self):
         """(box3x3, periodic) the list is binned and searched on: the system's box, or -- under a BrickDomain with a local cell
         grid -- the brick + its ghost layer, not periodic along the decomposed axes (brick.BrickDomain.nlist_box)."""
@@ -222,22 +236,24 @@ class CellNlist:
             return self.domain.nlist_box()
         return self.sys.box3x3, self.sys.periodic
 
-    def build(self):
-        s = self.sys
-        if self.domain is not None:
-            self.domain.rebuild()  # Communicator: migrate particles, re-plan + fill ghosts
+    def _size_grid(self):
+        """The cell grid of the search box into the descriptor, and the scratch a rebuild on it needs -> Ntot."""
+        s, d = self.sys, self._desc
         b3, per = self._search_box()
-        if getattr(self, "_sbox_key", None) != (b3.tobytes(), per):
-            self._sbox_key = (np.asarray(b3).tobytes(), per)
-            self._sbox = _lib.make_box(np.asarray(b3), per)
-        sbox = self._sbox
-        Ntot = s.N + s.n_ghost
+        key = (np.asarray(b3).tobytes(), per)
+        if self._sbox_key != key:
+            self._sbox_key = key
+            d.box = _lib.make_box(np.asarray(b3), per)
         n, w = self._ncell()
-        n3 = (C.c_int * 3)(*[int(x) for x in n])
-        w3 = (C.c_int * 3)(*[int(x) for x in w])
         ncell = int(n[0] * n[1] * n[2])
-        stream = C.c_void_p(raw_stream(s.device.index))
-        if getattr(self, "_scr_n", None) != (Ntot, ncell, int(w[1]), int(w[2])):
+        Ntot = s.N + s.n_ghost
+        d.r_list = self.r_list
+        d.ncell3[:] = [int(x) for x in n]
+        d.stencil3[:] = [int(x) for x in w]
+        # the period of the coordinates along the axes the domain's local grid is not periodic on (htfs_nlist's image_L)
+        lengths = getattr(self.domain, "image_lengths", None)
+        d.image_L[:] = lengths() if lengths is not None else (0.0, 0.0, 0.0)
+        if self._scr_n != (Ntot, ncell, int(w[1]), int(w[2])):
             self._scr_n = (Ntot, ncell, int(w[1]), int(w[2]))
             self._cell_of = torch.empty(Ntot, dtype=torch.int32, device=s.device)
             self._order = torch.empty(Ntot, dtype=torch.int32, device=s.device)
@@ -247,60 +263,63 @@ class CellNlist:
             # candidate ranges per (cell, stencil row): this list's own table (htf_standin.h HTFS_RANGE_WORDS), part of what a
             # captured step carries by address
             self._ranges = torch.empty(4 * ncell * int((2 * w[1] + 1) * (2 * w[2] + 1)), dtype=torch.int32, device=s.device)
-        cell_of, order, cell_start, pos_sorted = self._cell_of, self._order, self._cell_start, self._pos_sorted
-        if (self.domain is not None and getattr(self.domain, "fixed_capacity", False) and self.n_builds > 0 and not self.sort_particles
-                and self._ref is not None and self._ref.shape[0] == s.N and self.nlist is not None and self.nlist.numel() == s.N * self.pitch):
-            # every rebuild after the first of a fixed-capacity system: nothing to size, nothing to read back -- binning, sorted
-            # copy, range table, search and commit in six launches (htfs_rebuild_nlist_ghosts) where the separate calls take ten
-            capturing = getattr(self, "_capturing", False)
-            if not capturing:
-                self._poll_row_overflow()   # the PREVIOUS build's largest row (pinned copy behind it): no wait
-            # the binning scratch is this object's own and every completed build leaves its counts zero (cell_order_kernel): no memset
-            clean = getattr(self, "_scratch_clean", None) == (self._bin_scratch.data_ptr(), ncell)
-            self._scratch_clean = None   # (a call that fails half way leaves the counts dirty: the next one zeroes them again)
-            check(lib.htfs_rebuild_nlist_ghosts(s.pos.data_ptr(), s.scalar_code, s.N, Ntot, C.byref(sbox), self.r_list, C.byref(n3), C.byref(w3),
-                                                cell_of.data_ptr(), self._bin_scratch.data_ptr(), cell_start.data_ptr(), order.data_ptr(),
-                                                pos_sorted.data_ptr(), self.pitch, int(self.type_split), self.n_neigh.data_ptr(),
-                                                self.head_list.data_ptr(), self.nlist.data_ptr(), self._max.data_ptr(), self._ref.data_ptr(),
-                                                None, self._ranges.data_ptr(), int(clean), self._image_lengths(), stream))
-            self._scratch_clean = (self._bin_scratch.data_ptr(), ncell)
-            if getattr(self, "_max_host", None) is None:
-                self._max_host = torch.zeros(1, dtype=torch.int32).pin_memory()
-            if not (capturing and getattr(self, "_mirrored", False)):   # (BrickRun: the next check kernel carries it to the host)
-                self._max_host.copy_(self._max, non_blocking=True)
-            if not capturing:
-                self._max_event = torch.cuda.Event()
-                self._max_event.record(torch.cuda.current_stream(s.device))
-            if self._rule is not None:
-                self._rule.reset()
-                self._dd_prev = None
-            self._grid = (n3, w3, ncell)
-            self.n_builds += 1
-            return
-        check(lib.htfs_cell_index(s.pos.data_ptr(), s.scalar_code, Ntot, C.byref(sbox), C.byref(n3),
-                                  cell_of.data_ptr(), stream))
+            d.cell_of, d.order, d.cell_start = self._cell_of.data_ptr(), self._order.data_ptr(), self._cell_start.data_ptr()
+            d.scratch, d.pos_sorted, d.ranges = self._bin_scratch.data_ptr(), self._pos_sorted.data_ptr(), self._ranges.data_ptr()
+        self._grid = (n, w, ncell)
+        return Ntot
+
+    def build(self):
+        s = self.sys
+        if self.domain is not None:
+            self.domain.rebuild()  # Communicator: migrate particles, re-plan + fill ghosts
+        Ntot = self._size_grid()
+        fixed = self.domain is not None and getattr(self.domain, "fixed_capacity", False)
+        if (fixed and self.n_builds > 0 and not self.sort_particles and self._ref is not None and self._ref.shape[0] == s.N
+                and self.nlist is not None and self.nlist.numel() == s.N * self.pitch):
+            self._rebuild_fixed(Ntot)
+        else:
+            self._build_sized(Ntot, fixed)
+        if self._rule is not None:  # displacements are measured from the new reference positions
+            self._rule.reset()
+            self._dd_prev = None
+        self.n_builds += 1
+
+    def _rebuild_fixed(self, Ntot):
+        """Every rebuild after the first of a fixed-capacity system: nothing to size, nothing to read back -- binning, sorted
+        copy, range table, search and commit in six launches (htfs_rebuild_nlist) where the separate calls take ten."""
+        self._poll_max()   # the PREVIOUS build's largest row (pinned copy behind it): no wait
+        self._enqueue_rebuild(Ntot, gated=False)
+        self._copy_max_late()
+
+    def _build_sized(self, Ntot, fixed):
+        """The first build (and any the host sizes): the stepwise calls, with the pitch estimated, the rows grown until the
+        largest fits -- read back -- and the particles renumbered in cell order where ``sort_particles`` asks for it."""
+        s, d = self.sys, self._desc
+        n, _, ncell = self._grid
+        cell_of = self._cell_of
+        stream = C.c_void_p(raw_stream(s.device.index))
+        check(lib.htfs_cell_index(s.pos.data_ptr(), s.scalar_code, Ntot, C.byref(d.box), C.byref(d.ncell3), d.cell_of, stream))
         if self.sort_particles and s.N > 0:
             key = cell_of[: s.N].to(torch.int64)
             if self.domain is not None and self.domain.world > 1:
                 # the slab layout [interior | left | both | right] (domain.py) carries the halo slices and
                 # the interior row range: renumber inside each class only
-                key = key + self.domain.row_classes() * int(n[0] * n[1] * n[2])
+                key = key + self.domain.row_classes() * ncell
             perm = torch.sort(key, stable=True)[1]
             s.pos[: s.N] = s.pos[: s.N].index_select(0, perm)
             s.vel = s.vel.index_select(0, perm)
             cell_of[: s.N] = cell_of[: s.N].index_select(0, perm)
         # bin the particles: counting sort by cell, ascending index inside a cell (deterministic)
-        check(lib.htfs_cell_sort(cell_of.data_ptr(), Ntot, ncell, self._bin_scratch.data_ptr(), cell_start.data_ptr(),
-                                 order.data_ptr(), stream))
+        self._scratch_clean = None
+        check(lib.htfs_cell_sort(d.cell_of, Ntot, ncell, d.scratch, d.cell_start, d.order, stream))
+        self._scratch_clean = (d.scratch, ncell)
         # cell members contiguous: coalesced candidate reads
-        fixed = self.domain is not None and getattr(self.domain, "fixed_capacity", False)
         if fixed:
             # fixed-capacity arrays (brick.py): inert rows are in no cell -- only the binned particles have an entry in ``order``
-            check(lib.htfs_gather4_tagged_live(pos_sorted.data_ptr(), s.pos.data_ptr(), order.data_ptr(), s.scalar_code, Ntot,
-                                               cell_start.data_ptr() + 4 * ncell, int(self.type_split), stream))
+            check(lib.htfs_gather4_tagged_live(d.pos_sorted, s.pos.data_ptr(), d.order, s.scalar_code, Ntot,
+                                               d.cell_start + 4 * ncell, int(self.type_split), stream))
         else:
-            check(lib.htfs_gather4_tagged(pos_sorted.data_ptr(), s.pos.data_ptr(), order.data_ptr(), s.scalar_code, Ntot,
-                                          int(self.type_split), stream))
+            check(lib.htfs_gather4_tagged(d.pos_sorted, s.pos.data_ptr(), d.order, s.scalar_code, Ntot, int(self.type_split), stream))
         if self.pitch is None:
             # a sphere of r_list at the mean density, with generous head-room
             L = s.box3x3[1] - s.box3x3[0]
@@ -309,9 +328,9 @@ class CellNlist:
             dims = int(np.sum(n > 1)) or 3
             est = rho * (4.0 / 3.0 * math.pi * self.r_list ** 3 if dims == 3 else math.pi * self.r_list ** 2 * L[2])
             self.pitch = max(8, int(math.ceil(est * 1.5 / 8.0)) * 8)
-        capturing = getattr(self, "_capturing", False)
-        if fixed and self.n_builds > 0 and not capturing:
-            self._poll_row_overflow()   # the PREVIOUS build's largest row (pinned copy behind it): no wait
+        late = fixed and self.n_builds > 0   # no read-back in a rebuild of a fixed-capacity system: an overflowing row is reported one build late
+        if late:
+            self._poll_max()
         while True:
             if self.n_neigh is None or self.n_neigh.shape[0] != s.N:
                 self.n_neigh = torch.zeros(s.N, dtype=torch.int32, device=s.device)
@@ -320,18 +339,9 @@ class CellNlist:
                     self.domain.attach_n_neigh(self.n_neigh)   # a rebuild empties the rows that became inert
             if self.nlist is None or self.nlist.numel() != s.N * self.pitch:
                 self.nlist = torch.empty(s.N * self.pitch, dtype=torch.int32, device=s.device)
-            check(lib.htfs_build_nlist(s.pos.data_ptr(), pos_sorted.data_ptr(), s.scalar_code, s.N, Ntot, C.byref(sbox), self.r_list,
-                                       C.byref(n3), C.byref(w3), cell_start.data_ptr(), self.pitch, int(self.type_split),
-                                       self.n_neigh.data_ptr(), self.head_list.data_ptr(), self.nlist.data_ptr(),
-                                       self._max.data_ptr(), self._ranges.data_ptr(), stream))
-            if fixed and self.n_builds > 0:
-                # no read-back in a rebuild of a fixed-capacity system: an overflowing row is reported one build late
-                if getattr(self, "_max_host", None) is None:
-                    self._max_host = torch.zeros(1, dtype=torch.int32).pin_memory()
-                self._max_host.copy_(self._max, non_blocking=True)
-                if not capturing:
-                    self._max_event = torch.cuda.Event()
-                    self._max_event.record(torch.cuda.current_stream(s.device))
+            check(lib.htfs_build_nlist(C.byref(d), s.pos.data_ptr(), s.scalar_code, s.N, stream))
+            if late:
+                self._copy_max_late()
                 break
             mx = int(self._max.item())
             if mx <= self.pitch:
@@ -339,74 +349,98 @@ class CellNlist:
             self.pitch = int(math.ceil(mx * 1.2 / 8.0)) * 8
         if self._ref is None or self._ref.shape[0] != s.N:
             self._ref = s.pos[: s.N].clone()
+            d.ref = self._ref.data_ptr()
         else:
             self._ref.copy_(s.pos[: s.N])
-        if self._rule is not None:  # displacements are measured from the new reference positions
-            self._rule.reset()
-            self._dd_prev = None
-        self._grid = (n3, w3, ncell)
-        self.n_builds += 1
+
+    def _enqueue_rebuild(self, Ntot, gated):
+        """The one route to a rebuild after the first: ONE C call on the descriptor.  ``gated``: behind the distance check,
+        decided on the device, status words to pinned memory (htf_standin.h htfs_check_rebuild_nlist); else unconditional."""
+        s, d = self.sys, self._desc
+        # the binning scratch is this object's own and every completed binning leaves its counts zero (cell_order_kernel): no memset
+        key = (d.scratch, self._grid[2])
+        clean = int(self._scratch_clean == key)
+        self._scratch_clean = None   # (a call that fails half way leaves the counts dirty: the next one zeroes them again)
+        stream = C.c_void_p(raw_stream(s.device.index))
+        if gated:
+            check(lib.htfs_check_rebuild_nlist(C.byref(d), s.pos.data_ptr(), s.scalar_code, s.N, Ntot, clean, self._disp.data_ptr(),
+                                               (self.r_buff / 2.0) ** 2, self._stat.data_ptr(), self._stat_host.data_ptr(), stream))
+        else:
+            check(lib.htfs_rebuild_nlist(C.byref(d), s.pos.data_ptr(), s.scalar_code, s.N, Ntot, clean, stream))
+        self._scratch_clean = key
+
+    # ------------------------------------------------------------------ row overflow, reported one check late
+    def _record(self):
+        """An event on the current stream, behind whatever was enqueued last."""
+        ev = torch.cuda.Event()
+        # (an explicit device index: without one torch asks the runtime for the device count on every call, ~8 us)
+        idx = self.sys.device.index
+        ev.record(torch.cuda.current_stream(idx if idx is not None else torch.cuda.current_device()))
+        return ev
+
+    def _poll_late(self, word, event, where):
+        """``word``: a pinned copy of a rebuild's largest row; ``event`` (None: the caller knows the copy has landed) was
+        recorded behind it a whole check period ago -- long since complete, no wait."""
+        if event is not None:
+            event.synchronize()
+        if word is not None and int(word[0]) > self.pitch:
+            raise RuntimeError("neighbor list row overflow (%d entries, pitch %d) in %s" % (int(word[0]), self.pitch, where))
+
+    def _poll_overflow(self, event=None):
+        """The previous device-decided check's largest row (``event``: a replay loop that keeps the events itself)."""
+        event, self._stat_event = (self._stat_event if event is None else event), None
+        if event is not None:
+            self._poll_late(self._stat_host, event, "a device-decided rebuild: construct CellNlist with a larger pitch")
+
+    def mark_check_enqueued(self):
+        """An event behind the check's read-back; _poll_overflow waits for it one check later."""
+        self._stat_event = self._record()
+
+    def _poll_max(self):
+        """The previous rebuild-without-read-back's largest row."""
+        if self._capturing:   # (no host-side waits inside a hipGraph capture)
+            return
+        event, self._max_event = self._max_event, None
+        if event is not None:
+            self._poll_late(self._max_host, event, "a rebuild without read-back: construct CellNlist with a larger pitch")
+
+    def _pinned_max(self):
+        if self._max_host is None:
+            self._max_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+        return self._max_host
+
+    def _copy_max_late(self):
+        """The largest row of the rebuild just enqueued -> pinned memory, an event behind it; read at the next rebuild."""
+        if not (self._capturing and self._mirrored):   # (BrickRun: the next check kernel carries it to the host)
+            self._pinned_max().copy_(self._max, non_blocking=True)
+        if not self._capturing:
+            self._max_event = self._record()
 
     # ------------------------------------------------------------------ device-side decision
     def _device_ok(self):
         return (self.device_decision and self._ref is not None and not self.sort_particles
                 and (self.domain is None or self.domain.world == 1) and self.sys.n_ghost == 0
-                and self._ref.shape[0] == self.sys.N and getattr(self, "_scr_n", (None,))[0] == self.sys.N)
-
-    def _poll_overflow(self):
-        """The previous check's (largest row, rebuild count), copied to pinned host memory behind it."""
-        if self._stat_event is not None:
-            self._stat_event.synchronize()  # recorded a whole check period ago: long since complete
-            self._stat_event = None
-            if int(self._stat_host[0]) > self.pitch:
-                raise RuntimeError("neighbor list row overflow (%d entries, pitch %d) in a device-decided rebuild: "
-                                   "construct CellNlist with a larger pitch" % (int(self._stat_host[0]), self.pitch))
-
-    def _poll_row_overflow(self):
-        ev = getattr(self, "_max_event", None)
-        if ev is not None:
-            ev.synchronize()
-            self._max_event = None
-            if int(self._max_host[0]) > self.pitch:
-                raise RuntimeError("neighbor list row overflow (%d entries, pitch %d) in a rebuild without read-back: construct "
-                                   "CellNlist with a larger pitch" % (int(self._max_host[0]), self.pitch))
+                and self._ref.shape[0] == self.sys.N and self._scr_n is not None and self._scr_n[0] == self.sys.N)
 
     def check_and_rebuild_on_device(self):
         """NeighborList::compute at a check step with the decision left to the device: distance check, then
         the whole rebuild gated on its result.  No host synchronisation."""
-        s = self.sys
-        capturing = getattr(self, "_capturing", False)  # inside Simulation's hipGraph capture: no host-side waits
-        if not capturing:
+        if not self._capturing:  # (inside a hipGraph capture: no host-side waits)
             self._poll_overflow()
         if self._stat is None:
-            self._stat = torch.zeros(2, dtype=torch.int32, device=s.device)  # [largest row of the last rebuild, rebuilds]
+            self._stat = torch.zeros(2, dtype=torch.int32, device=self.sys.device)  # [largest row of the last rebuild, rebuilds]
             self._stat_host = torch.zeros(2, dtype=torch.int32).pin_memory()
-        n3, w3, ncell = self._grid
-        stream = C.c_void_p(raw_stream(s.device.index))
-        # distance check, gate, index + sort + sorted copy + search + commit behind it, status words to pinned memory: one call
-        # (htf_standin.h htfs_check_rebuild_nlist -- a dozen Python-level calls and torch ops before)
-        check(lib.htfs_check_rebuild_nlist(s.pos.data_ptr(), s.scalar_code, s.N, C.byref(s.box), self.r_list, C.byref(n3), C.byref(w3),
-                                           self._cell_of.data_ptr(), self._bin_scratch.data_ptr(), self._cell_start.data_ptr(),
-                                           self._order.data_ptr(), self._pos_sorted.data_ptr(), self.pitch, int(self.type_split),
-                                           self.n_neigh.data_ptr(), self.head_list.data_ptr(), self.nlist.data_ptr(),
-                                           self._stat.data_ptr(), self._ref.data_ptr(), self._disp.data_ptr(),
-                                           (self.r_buff / 2.0) ** 2, self._stat_host.data_ptr(), self._ranges.data_ptr(), stream))
-        if not capturing:
+        self._enqueue_rebuild(self.sys.N, gated=True)
+        if not self._capturing:
             self.mark_check_enqueued()
 
-    def mark_check_enqueued(self):
-        """An event behind the check's read-back; _poll_overflow waits for it one check later."""
-        self._stat_event = torch.cuda.Event()
-        # (an explicit device index: without one torch asks the runtime for the device count on every call, ~8 us)
-        idx = self.sys.device.index
-        self._stat_event.record(torch.cuda.current_stream(idx if idx is not None else torch.cuda.current_device()))
-
     def graph_key(self):
-        """Addresses of every buffer a captured check + rebuild carries by value (Simulation._run_graphed)."""
-        bufs = (self.n_neigh, self.head_list, self.nlist, self._ref, self._disp, self._stat, self._stat_host,
-                getattr(self, "_cell_of", None), getattr(self, "_order", None), getattr(self, "_cell_start", None),
-                getattr(self, "_bin_scratch", None), getattr(self, "_pos_sorted", None), getattr(self, "_ranges", None))
-        return tuple(0 if b is None else b.data_ptr() for b in bufs) + (int(self.type_split), self.check_period)
+        """Addresses of every buffer a captured check + rebuild carries by value (Simulation._run_graphed): the descriptor's
+        pointer fields and the check's own words."""
+        d = self._desc
+        return (tuple(getattr(d, name) or 0 for name, ctype in d._fields_ if ctype is C.c_void_p)
+                + tuple(0 if b is None else b.data_ptr() for b in (self._disp, self._stat, self._stat_host))
+                + (int(self.type_split), self.check_period))
 
     def device_builds(self):
         """Rebuilds the device has decided on so far (synchronises; for reports, not for the step loop)."""
@@ -479,14 +513,14 @@ class CellNlist:
             # every rank must take the same rebuild decision (the rebuild communicates)
             import torch.distributed as dist
             dist.all_reduce(self._disp, op=dist.ReduceOp.MAX, group=self.domain.group)
-        # the threshold in fp32, as the device-side gate compares it (htfs_set_gate)
+        # the threshold in fp32, as the device-side gate compares it (htfs_check_rebuild_nlist)
         return float(self._disp.item()) > float(np.float32((self.r_buff / 2.0) ** 2))
 
     def compute(self, timestep):
         """NeighborList::compute(timestep): rebuild if the distance check trips.  Under domain
         decomposition a second compute sharing this list in the same step finds the step's
         check / halo already done (HOOMD's NeighborList caches per timestep too)."""
-        if self.domain is not None and self._ref is not None and getattr(self, "_step_done", None) == timestep:
+        if self.domain is not None and self._ref is not None and self._step_done == timestep:
             return
         self._step_done = timestep
         if self._device_ok():
@@ -652,6 +686,8 @@ class Simulation:
         self.computes = []   # system.addCompute(...) without forces
         self.integrator = None
         self.nlists = []     # the neighbor lists made by nlist_cell (center_of_mass asks whether one sorts particles)
+        self._graph = self._graph_key = None   # the captured check period and everything it carries by value
+        self._no_graph = False                 # the step turned out not to capture
         _current["sim"] = self
 
     def nlist_cell(self, r_buff=0.4, check_period=1, pitch=None, device_decision=True):
@@ -714,12 +750,12 @@ class Simulation:
         key = (id(f), id(nl), id(self.integrator), cycle, s.N, nl.pitch, f.graph_key(), float(self.integrator.dt), float(nl.r_list),
                float(nl.r_buff), tuple(float(x) for x in np.asarray(s.box3x3).ravel()), s.pos.data_ptr(), s.vel.data_ptr(),
                s.force.data_ptr(), nl.graph_key())
-        if getattr(self, "_graph_key", None) != key:
+        if self._graph_key != key:
             torch.cuda.synchronize()
             nl._poll_overflow()
             g = torch.cuda.CUDAGraph()
             ts0 = s.timestep
-            host_counters = (getattr(f, "_calls", 0), getattr(nl, "_step_done", None))  # what recording the cycle advances
+            host_counters = (getattr(f, "_calls", 0), nl._step_done)  # what recording the cycle advances
             nl._capturing = True
             try:
                 with torch.cuda.graph(g):
@@ -751,20 +787,16 @@ class Simulation:
         n_replay = 0
         while nsteps >= cycle:
             if n_replay % every == 0 and len(behind) >= 2:
-                nl._stat_event = behind.pop(0)
-                nl._poll_overflow()
+                nl._poll_overflow(behind.pop(0))
             self._graph.replay()
             f._calls = getattr(f, "_calls", 0) + cycle
             s.timestep += cycle
             nsteps -= cycle
             if n_replay % every == 0:
-                nl.mark_check_enqueued()
-                behind.append(nl._stat_event)
-                nl._stat_event = None
+                behind.append(nl._record())
             n_replay += 1
         for ev in behind:
-            nl._stat_event = ev
-            nl._poll_overflow()
+            nl._poll_overflow(ev)
         return nsteps
 
     def _step(self):
@@ -828,9 +860,9 @@ class Simulation:
         auto = graph is None and env != "1"
         if graph is None:
             graph = env == "1"
-            if env not in ("0", "1") and nsteps >= 256 and self.system.pos.is_cuda and not getattr(self, "_no_graph", False):
+            if env not in ("0", "1") and nsteps >= 256 and self.system.pos.is_cuda and not self._no_graph:
                 choice = getattr(self, "graph_choice", None)
-                if choice is None or (choice["key"] is not None and choice["key"] != getattr(self, "_graph_key", None)):
+                if choice is None or (choice["key"] is not None and choice["key"] != self._graph_key):
                     nsteps -= self._choose_by_measurement(nsteps)
                     choice = getattr(self, "graph_choice", None)
                 graph = bool(choice and choice["use_graph"])
@@ -864,6 +896,7 @@ class BrickRun:
             raise ValueError("BrickRun drives a CellNlist whose domain is a BrickDomain")
         self._graphs = None
         self._mirror = None
+        self._rule = None
         self.n_rebuild_cycles = 0
         self.n_cycles = 0
         self._fstep = None
@@ -956,11 +989,9 @@ class BrickRun:
         # the status words the host reads one cycle late travel with the check kernel (HTF_BRICK_MIRROR=0: a copy node each, as before)
         self._mirror = None
         if os.environ.get("HTF_BRICK_MIRROR", "1") != "0":
-            if getattr(nl, "_max_host", None) is None:
-                nl._max_host = torch.zeros(1, dtype=torch.int32).pin_memory()
             m = _lib.Mirror()
             m.src[0], m.dst[0], m.words[0] = dom.counts.data_ptr(), dom._flags_host.data_ptr(), _lib.BC_WORDS
-            m.src[1], m.dst[1], m.words[1] = nl._max.data_ptr(), nl._max_host.data_ptr(), 1
+            m.src[1], m.dst[1], m.words[1] = nl._max.data_ptr(), nl._pinned_max().data_ptr(), 1
             m.n = 2
             self._mirror = m
         nl._mirrored = dom._mirrored = self._mirror is not None
@@ -1009,9 +1040,7 @@ class BrickRun:
         d2 = float(h[0])
         # cycle - 1 is complete: what its rebuild (if any) reported
         self.dom._raise_flags(int(self.dom._flags_host[_lib.BC_FLAGS]))
-        mh = getattr(self.nl, "_max_host", None)
-        if mh is not None and int(mh[0]) > self.nl.pitch:
-            raise RuntimeError("neighbor list row overflow (%d entries, pitch %d) in a replayed rebuild" % (int(mh[0]), self.nl.pitch))
+        self.nl._poll_late(self.nl._max_host, None, "a replayed rebuild")
         return d2
 
     def run(self, nsteps, graph=False):
@@ -1066,4 +1095,4 @@ class BrickRun:
 
     @property
     def dangerous_builds(self):
-        return self._rule.dangerous if getattr(self, "_rule", None) is not None else self.nl.dangerous_builds
+        return self._rule.dangerous if self._rule is not None else self.nl.dangerous_builds

@@ -33,7 +33,7 @@ extern "C" {
  * caller's candidate-range table).  Every binding compares the value it was built against with
  * htf_abi_version() of the library it loaded and refuses a mismatch: hoomd_tf_amd/_lib.py, csrc/pybind_abi.cc,
  * integration/hoomd_shim/TensorflowComputeAMD.cc. */
-#define HTF_AMD_ABI_VERSION 4
+#define HTF_AMD_ABI_VERSION 5
 
 /* the library is built with -fvisibility=hidden (as the reference is,
  * htf/CMakeLists.txt:48); only these entry points are exported */

@@ -37,93 +37,77 @@ typedef struct htfs_mirror {
 HTF_API int htfs_check_displacement2(const void *d_pos, const void *d_ref, int dtype, unsigned N, const htf_box *box,
                                      unsigned *d_work, float *d_out, float *h_out, const htfs_mirror *mirror, htf_stream stream);
 
-/* Cell-list neighbor search in HOOMD layout (NeighborListGPUBinned analogue).
- * d_pos_sorted [Ntot] (htfs_gather4_tagged: pos[order] with the particle's index in w, so a cell's
- * members are contiguous and one load brings a candidate's position and identity) and d_cell_start
- * [ncell+1] are produced by the caller (binning + sort + gather are plumbing); this kernel walks
- * the neighbor cells of each local particle -- stencil3[d] = 0 (one cell along d), 1 (cells at
- * least r_list wide, 3 per direction) or 2 (at least r_list / 2 wide, 5 per direction) -- and writes
+/* Cell-list neighbor search in HOOMD layout (NeighborListGPUBinned analogue): everything that describes a list between
+ * rebuilds.  The caller owns every buffer; a hipGraph that has captured a rebuild carries these addresses by value.
+ * The search walks the neighbor cells of each local particle -- stencil3[d] = 0 (one cell along d), 1 (cells at least r_list
+ * wide, 3 per direction) or 2 (at least r_list / 2 wide, 5 per direction) -- in the cell-sorted copy and writes
  *   nlist[i*pitch + c] = k  for every k != i with |minimage(r_k - r_i)| <= r_list,
- *   n_neigh[i] = count, head_list[i] = i*pitch.
- * *d_max_neigh is set to the largest count (> pitch means the list overflowed and must be
- * rebuilt with a larger pitch; a call the gate below holds back leaves the previous value).  type_split >= 0: pairs whose types lie on different
- * sides of it are left out (hoomd.md.nlist.rcut set_pair(..., -1) between all-atom and mapped
- * bead types, tensorflowcompute.py:284-305); -1: no type filter.
- * d_ranges: the caller's candidate-range table, 16-byte aligned, 4 * ncell * (2 stencil3[1] + 1) * (2 stencil3[2] + 1) words
- * (HTFS_RANGE_WORDS).  Every call rewrites it before the search reads it; it belongs to the list (ABI 3: until then a
- * thread-local buffer of the library, re-allocated under any hipGraph that had captured its address). */
+ *   n_neigh[i] = count, head_list[i] = i*pitch. */
 #define HTFS_RANGE_WORDS(ncell, stencil_y, stencil_z) (4u * (size_t)(ncell) * (2u * (stencil_y) + 1u) * (2u * (stencil_z) + 1u))
-HTF_API int htfs_build_nlist(const void *d_pos, const void *d_pos_sorted, int dtype, unsigned N, unsigned Ntot,
-                             const htf_box *box, double r_list, const int *ncell3, const int *stencil3,
-                             const unsigned *d_cell_start, unsigned pitch, int type_split,
-                             unsigned *d_n_neigh, unsigned *d_head_list, unsigned *d_nlist, unsigned *d_max_neigh,
-                             void *d_ranges, htf_stream stream);
+typedef struct htfs_nlist {
+    htf_box box;            /* the box the list is binned and searched on (a brick + its ghost layer under a local grid) */
+    double r_list;
+    int ncell3[3];          /* cells per direction, x fastest; ncell = their product */
+    int stencil3[3];
+    unsigned pitch;
+    int type_split;         /* >= 0: pairs whose types lie on different sides of it are left out (hoomd.md.nlist.rcut
+                             * set_pair(..., -1) between all-atom and mapped bead types, tensorflowcompute.py:284-305); -1: no filter */
+    /* scratch of a rebuild, Ntot = local rows + ghosts */
+    unsigned *cell_of;      /* [Ntot] cell index of every particle; 0xFFFFFFFF for an INERT row (x = NaN: fixed-capacity arrays of
+                             * a decomposed system, hoomd_tf_amd/brick.py -- such rows are in no cell) */
+    unsigned *scratch;      /* [2 * ncell], 16-byte aligned (checked).  Its first half (the per-cell counts) is zero after every
+                             * COMPLETED binning on it with the same ncell, as long as nothing else has written the buffer: that is
+                             * what a caller passing scratch_clean != 0 promises, and the call then skips its memset (two dependent
+                             * nodes of a captured rebuild; a rebuild a closed gate holds back does not touch the counts either) */
+    unsigned *cell_start;   /* [ncell + 1] first slot of cell c; the last word is the binned total */
+    unsigned *order;        /* [Ntot] particle indices sorted by cell, ascending index inside a cell (deterministic) */
+    void *pos_sorted;       /* [Ntot] Scalar4 pos[order] with  order[i] | (type >= type_split) << 31  in w (Ntot <= 2^31): a cell's
+                             * members are contiguous and one load brings a candidate's position and identity */
+    void *ranges;           /* HTFS_RANGE_WORDS(ncell, stencil3[1], stencil3[2]) words, 16-byte aligned: the candidate-range table.
+                             * Every rebuild rewrites it before the search reads it */
+    /* outputs */
+    unsigned *n_neigh;      /* [N] */
+    unsigned *head_list;    /* [N] */
+    unsigned *nlist;        /* [N * pitch] */
+    unsigned *max_neigh;    /* the largest count (> pitch: the list overflowed and must be rebuilt with a larger pitch); a
+                             * rebuild a closed gate holds back leaves the previous value */
+    void *ref;              /* nullable: [N] Scalar4 <- pos at a rebuild (what htfs_max_displacement2 measures from) */
+    unsigned *counter;      /* nullable: += 1 at a rebuild */
+    double image_L[3];      /* 0 = leave the axis alone.  Along an axis the grid is NOT periodic on, the period the caller's
+                             * coordinates have -- the logical box length of a decomposed system -- so that a coordinate is binned,
+                             * and copied into pos_sorted, as its image nearest the grid's centre (a row that left the brick through a
+                             * face on the box boundary was wrapped to the far side by the integrator; the search measures plain
+                             * differences along such an axis) */
+} htfs_nlist;
 
-/* dest[i] = src[order[i]] for Scalar4 arrays: the cell-sorted position copy */
-/* Cell binning: d_order <- particle indices sorted by cell (ascending index inside a cell: deterministic),
- * d_cell_start[c] <- first slot of cell c (ncell + 1 entries).  d_scratch: 2 * ncell words, 16-byte aligned (checked).  Its
- * first half (the per-cell counts) is left zeroed by every call that runs; a call under htfs_set_gate clears it again only
- * when the calling thread's last call on this scratch used another ncell (or there was none). */
-HTF_API int htfs_cell_sort(const unsigned *d_cell_of, unsigned Ntot, unsigned ncell, unsigned *d_scratch,
-                           unsigned *d_cell_start, unsigned *d_order, htf_stream stream);
-HTF_API int htfs_gather4(void *d_dest, const void *d_src, const int *d_order, int dtype, unsigned n, htf_stream stream);
-/* the same with w replaced by  order[i] | (type >= type_split) << 31  (type_split < 0: the index alone; n <= 2^31):
- * the candidate array htfs_build_nlist reads, called with the same type_split */
-HTF_API int htfs_gather4_tagged(void *d_dest, const void *d_src, const int *d_order, int dtype, unsigned n, int type_split,
-                                htf_stream stream);
-
-/* the same for arrays with INERT rows (x = NaN: fixed-capacity arrays of a decomposed system, hoomd_tf_amd/brick.py -- such rows
- * are in no cell, htfs_cell_index gives them 0xFFFFFFFF and htfs_cell_sort leaves them out): only the first *d_n_live entries of
- * d_order exist, d_n_live = d_cell_start + ncell (the binned total), read on the device */
-HTF_API int htfs_gather4_tagged_live(void *d_dest, const void *d_src, const int *d_order, int dtype, unsigned n_max,
-                                     const unsigned *d_n_live, int type_split, htf_stream stream);
-
-/* cell index of every particle (x fastest): d_cell_of[i] */
+/* The stepwise form, for a first build that sizes its buffers between the steps.  cell index of every particle: */
 HTF_API int htfs_cell_index(const void *d_pos, int dtype, unsigned Ntot, const htf_box *box,
                             const int *ncell3, unsigned *d_cell_of, htf_stream stream);
-
-/* Conditional rebuild WITHOUT a host decision: after htfs_set_gate(d_disp2, threshold2) every binning /
- * search kernel of this header launched by the calling thread (htfs_cell_index, htfs_cell_sort, htfs_gather4[_tagged],
- * htfs_build_nlist, htfs_commit_rebuild) returns at entry unless *d_disp2 > threshold2 when it RUNS, with
- * d_disp2 the word htfs_max_displacement2 has just filled on the same stream; htfs_set_gate(NULL, 0) ends
- * it.  The caller enqueues the whole rebuild behind every distance check and never reads the result back. */
-HTF_API int htfs_set_gate(const float *d_disp2, double threshold2);
-
-/* Tail of a rebuild (gated like the rest): ref[i] = pos[i] for i < N, and *d_counter (nullable) += 1. */
-HTF_API int htfs_commit_rebuild(void *d_ref, const void *d_pos, int dtype, unsigned N, unsigned *d_counter,
+/* counting sort by cell: htfs_nlist's order and cell_start from cell_of; d_scratch as htfs_nlist's, always zeroed first */
+HTF_API int htfs_cell_sort(const unsigned *d_cell_of, unsigned Ntot, unsigned ncell, unsigned *d_scratch,
+                           unsigned *d_cell_start, unsigned *d_order, htf_stream stream);
+/* htfs_nlist's pos_sorted from pos and order */
+HTF_API int htfs_gather4_tagged(void *d_dest, const void *d_src, const int *d_order, int dtype, unsigned n, int type_split,
                                 htf_stream stream);
+/* the same for arrays with inert rows: only the first *d_n_live entries of d_order exist, d_n_live = d_cell_start + ncell (the
+ * binned total), read on the device */
+HTF_API int htfs_gather4_tagged_live(void *d_dest, const void *d_src, const int *d_order, int dtype, unsigned n_max,
+                                     const unsigned *d_n_live, int type_split, htf_stream stream);
+/* range table + search of the N local rows of d_pos, on cell_start and pos_sorted as the calls above left them */
+HTF_API int htfs_build_nlist(const htfs_nlist *nl, const void *d_pos, int dtype, unsigned N, htf_stream stream);
 
-/* htfs_cell_index + htfs_cell_sort + htfs_gather4_tagged + htfs_build_nlist + htfs_commit_rebuild of a single-domain system
- * (N particles, no ghosts) on the same arguments, in six launches instead of nine; gated like them.  d_scratch: as
- * htfs_cell_sort's; d_ranges: as htfs_build_nlist's; d_ref / d_counter nullable. */
-HTF_API int htfs_rebuild_nlist(const void *d_pos, int dtype, unsigned N, const htf_box *box, double r_list, const int *ncell3,
-                               const int *stencil3, unsigned *d_cell_of, unsigned *d_scratch, unsigned *d_cell_start,
-                               unsigned *d_order, void *d_pos_sorted, unsigned pitch, int type_split, unsigned *d_n_neigh,
-                               unsigned *d_head_list, unsigned *d_nlist, unsigned *d_max_neigh, void *d_ref,
-                               unsigned *d_counter, void *d_ranges, htf_stream stream);
+/* The whole rebuild in one call and six launches (the stepwise calls take ten): Ntot >= N positions binned, the N local rows
+ * searched, ref and counter committed. */
+HTF_API int htfs_rebuild_nlist(const htfs_nlist *nl, const void *d_pos, int dtype, unsigned N, unsigned Ntot, int scratch_clean,
+                               htf_stream stream);
 
-/* the same with ghosts (and inert rows): Ntot >= N positions are binned, the N local rows searched and committed.
- * scratch_clean != 0: the caller guarantees that the first ncell words of d_scratch are zero -- they are after any COMPLETED
- * htfs_cell_sort / htfs_rebuild_nlist* call on this scratch with the same ncell, as long as nothing else has written the buffer --
- * and the call skips its memset (two dependent nodes of a captured rebuild).
- * image_L (nullable, 3 doubles on the host; 0 = leave the axis alone): along an axis the grid is NOT periodic on, the period the
- * caller's coordinates have -- the logical box length of a decomposed system -- so that a coordinate is binned, and copied into
- * d_pos_sorted, as its image nearest the grid's centre (a row that left the brick through a face on the box boundary was wrapped
- * to the far side by the integrator; the search measures plain differences along such an axis). */
-HTF_API int htfs_rebuild_nlist_ghosts(const void *d_pos, int dtype, unsigned N, unsigned Ntot, const htf_box *box, double r_list,
-                                      const int *ncell3, const int *stencil3, unsigned *d_cell_of, unsigned *d_scratch,
-                                      unsigned *d_cell_start, unsigned *d_order, void *d_pos_sorted, unsigned pitch, int type_split,
-                                      unsigned *d_n_neigh, unsigned *d_head_list, unsigned *d_nlist, unsigned *d_max_neigh, void *d_ref,
-                                      unsigned *d_counter, void *d_ranges, int scratch_clean, const double *image_L, htf_stream stream);
-
-/* One check step of a device-decided list in one call: *d_disp2 <- 0, htfs_max_displacement2 into it, htfs_set_gate(d_disp2,
- * threshold2), htfs_rebuild_nlist (d_stat2[0] = largest row, d_stat2[1] = rebuild counter), htfs_set_gate(NULL, 0), and -- if
- * h_stat2 (pinned host memory) is given -- an asynchronous copy of the two status words for a later check to read. */
-HTF_API int htfs_check_rebuild_nlist(const void *d_pos, int dtype, unsigned N, const htf_box *box, double r_list, const int *ncell3,
-                                     const int *stencil3, unsigned *d_cell_of, unsigned *d_scratch, unsigned *d_cell_start,
-                                     unsigned *d_order, void *d_pos_sorted, unsigned pitch, int type_split, unsigned *d_n_neigh,
-                                     unsigned *d_head_list, unsigned *d_nlist, unsigned *d_stat2, void *d_ref, float *d_disp2,
-                                     double threshold2, unsigned *h_stat2, void *d_ranges, htf_stream stream);
+/* One check step of a device-decided list in one call, WITHOUT a host decision: *d_disp2 <- 0, htfs_max_displacement2 (from
+ * nl->ref, required) into it, then the rebuild above with every kernel returning at entry unless *d_disp2 > threshold2 when it
+ * RUNS; the caller enqueues it behind every distance check and never reads the result back.  d_stat2 stands in for
+ * nl->max_neigh and nl->counter (d_stat2[0] = largest row, d_stat2[1] = rebuilds); h_stat2 (nullable; pinned host memory)
+ * receives an asynchronous copy of the two words for a later check to read. */
+HTF_API int htfs_check_rebuild_nlist(const htfs_nlist *nl, const void *d_pos, int dtype, unsigned N, unsigned Ntot, int scratch_clean,
+                                     float *d_disp2, double threshold2, unsigned *d_stat2, unsigned *h_stat2, htf_stream stream);
 
 /* Slab decomposition (the stand-in for HOOMD's Communicator; hoomd_tf_amd/domain.py): the migration + ghost plan of a
  * rebuild.  d_key[i] = destination * 4 + ghost class of local particle i (destination: 0 stay, 1 left neighbor,

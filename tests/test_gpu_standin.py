@@ -434,7 +434,7 @@ def test_slab_plan_kernels_match_torch(htf, cuda):
 
 
 def test_rebuild_on_a_non_periodic_grid_takes_the_nearest_image(htf, cuda):
-    """htfs_rebuild_nlist_ghosts' image_L: on a cell grid that is NOT periodic along x while the coordinates are (a decomposed system's
+    """htfs_nlist's image_L: on a cell grid that is NOT periodic along x while the coordinates are (a decomposed system's
     brick + ghost layer), rows whose x is a whole period away -- wrapped to the far side of the logical box by the integrator after
     they left through a face on its boundary, or the ghosts of such rows -- are binned and searched as their image next to the
     grid: the neighbor rows of EVERY particle equal those of the same configuration with nothing shifted."""

@@ -18,6 +18,7 @@
 #include "htf_geom.h"
 #include "htf_nlist.h"
 #include "htf_desc.h"
+#include "htf_desc_train.h"
 
 namespace py = pybind11;
 
@@ -178,6 +179,11 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
     X(htf_desc_forces) \
     X(htf_desc_descriptor)
 
+// include/htf_desc_train.h: force matching for the descriptor network (_lib.DESC_TRAIN_PROTOTYPES)
+#define HTF_DESC_TRAIN_FUNCTIONS(X) \
+    X(htf_dtrain_scratch_floats) \
+    X(htf_dtrain_loss_grad)
+
 PYBIND11_MODULE(_htf_abi, m) {
     m.doc() = "pybind11 binding of libhtf_amd.so's C ABI: pointers as integers";
     // a stale module (or library): this module's templates were instantiated from one header, the library it resolved at load
@@ -192,5 +198,6 @@ PYBIND11_MODULE(_htf_abi, m) {
     HTF_GEOM_FUNCTIONS(X)
     HTF_NLIST_FUNCTIONS(X)
     HTF_DESC_FUNCTIONS(X)
+    HTF_DESC_TRAIN_FUNCTIONS(X)
 #undef X
 }

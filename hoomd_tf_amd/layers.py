@@ -305,15 +305,26 @@ class DescriptorMLP:
     'linear' for both hidden layers.  The weights (``mlp_params(seed, K=n_types*K, H1, H2)``, Keras order) live in one flat
     fp32 device tensor ``w`` that the kernel reads at every call: ``set_weights``, ``load_weights`` and in-place writes to
     ``w`` take effect at the next call.  The energy takes no part in arithmetic with other energies (it raises): evaluate
-    each term with its own ``compute_nlist_forces`` and add the forces.  The layer is not trainable.
+    each term with its own ``compute_nlist_forces`` and add the forces.
+
+    ``trainable=True`` makes the layer learn by force matching (include/htf_desc_train.h): under ``tfcompute.attach(...,
+    train=True)`` every batch is one ``loss_gradient`` sweep -- the sum of squared residuals of (F_i, E_i) against the
+    labels and its gradient with respect to ``w``, one pass over the pair vectors -- and one optimizer step on ``w``, on
+    the device.  ``loss_gradient`` is also the offline entry: with ``iter_from_trajectory`` and ``ops.optimizer_step`` on
+    ``w`` it trains from stored frames.  The centres and their spacing are not trained.  With the default
+    ``trainable=False`` a training run raises.
     Limits: ``n_types * K <= 64``, ``H1, H2 <= 64``, at most 256 neighbor slots."""
 
     name = 'descriptor-mlp'
     _KEYS = ("W1", "b1", "W2", "b2", "W3", "b3")
     MAX_D, MAX_H, MAX_NN = 64, 64, 256
+    nonneg_mask = 0     # what the optimizer step reads of a trainable layer: no weight is constrained or regularised
+    l1_reg = (0.0,)
 
-    def __init__(self, K=16, H1=32, H2=32, low=0.0, high=3.0, n_types=1, activation="tanh", seed=3, device=None):
+    def __init__(self, K=16, H1=32, H2=32, low=0.0, high=3.0, n_types=1, activation="tanh", seed=3, device=None,
+                 trainable=False):
         K, H1, H2, n_types = int(K), int(H1), int(H2), int(n_types)
+        self.trainable = bool(trainable)
         activation = activation or "linear"
         if activation not in ("tanh", "linear"):
             raise ValueError("DescriptorMLP: activation must be 'tanh' or 'linear', not %r" % (activation,))
@@ -337,8 +348,11 @@ class DescriptorMLP:
         self.mu = torch.tensor(self.centers, dtype=torch.float32, device=device)
 
     def get_config(self):
-        return {'K': self.K, 'H1': self.H1, 'H2': self.H2, 'low': self.low, 'high': self.high, 'n_types': self.n_types,
-                'activation': self.activation}
+        cfg = {'K': self.K, 'H1': self.H1, 'H2': self.H2, 'low': self.low, 'high': self.high, 'n_types': self.n_types,
+               'activation': self.activation}
+        if self.trainable:
+            cfg['trainable'] = True
+        return cfg
 
     def get_weights(self):
         flat, out, o = self.w.detach().cpu().numpy(), [], 0
@@ -389,6 +403,38 @@ class DescriptorMLP:
                                   self.mu.data_ptr(), float(self.gap), out.data_ptr(), ops._dt(out),
                                   v.data_ptr() if v is not None else None, ops._stream(x)))
         return (out, v) if virial else out
+
+    def loss_gradient(self, x, labels, pred=None, accum=None):
+        """One force-matching sweep (htf_dtrain_loss_grad) over a pair-vector tensor ``x`` [B, NN, 4] (fp32 or fp64) and
+        ``labels`` [B, 4] (fp32 or fp64): returns ``accum`` [1 + P] fp32 on the device, {sum of squared residuals of
+        (F_i, E_i), its gradient with respect to ``w``} -- what ``ops.optimizer_step(w, accum, 1 / (4 B), ...)`` consumes for
+        Keras' MeanSquaredError.  ``pred`` [B, 4] fp32: the layer's ``forces(x)`` at the current weights, evaluated here
+        when not given.  Two calls on the same inputs give the same bits."""
+        B, NN = self._check(x)
+        ops._dev(labels, "labels")
+        ops._dt(labels)
+        if tuple(labels.shape) != (B, 4) or labels.device != x.device:
+            raise ValueError("DescriptorMLP: labels must be [%d, 4] on %s, got %s on %s" % (B, x.device, tuple(labels.shape), labels.device))
+        if pred is None:
+            pred = self.forces(x)
+            if pred.dtype != torch.float32:
+                pred = pred.to(torch.float32)
+        ops._dev(pred, "pred", torch.float32)
+        if tuple(pred.shape) != (B, 4) or pred.device != x.device:
+            raise ValueError("DescriptorMLP: pred must be [%d, 4] on %s, got %s on %s" % (B, x.device, tuple(pred.shape), pred.device))
+        P = int(self.w.numel())
+        if accum is None:
+            accum = torch.empty(1 + P, dtype=torch.float32, device=x.device)
+        ops._dev(accum, "accum", torch.float32)
+        if accum.numel() != 1 + P or accum.device != x.device:
+            raise ValueError("DescriptorMLP: accum must hold %d floats on %s" % (1 + P, x.device))
+        scratch = torch.empty(int(lib.htf_dtrain_scratch_floats(B, self.K, self.n_types, self.H1, self.H2)), dtype=torch.float32,
+                              device=x.device)
+        act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
+        check(lib.htf_dtrain_loss_grad(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, self.w.data_ptr(),
+                                       self.mu.data_ptr(), float(self.gap), labels.data_ptr(), ops._dt(labels), pred.data_ptr(),
+                                       accum.data_ptr(), scratch.data_ptr(), ops._stream(x)))
+        return accum
 
     def descriptor(self, nlist):
         """G [B, D] alone (the kernel's first stage), in the dtype of the pair-vector tensor."""

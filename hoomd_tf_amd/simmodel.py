@@ -1701,11 +1701,16 @@ def compute_nlist_forces(nlist, energy, virial=False):
         raise ValueError('Could not find dependence between energy and nlist.'
                          ' Did you put them in wrong order?')
     if isinstance(energy, DescriptorEnergy):
-        if getattr(_trace, "training_graph", False):
-            raise NotImplementedError("DescriptorMLP is not trainable: neither tfcompute(train=True) nor train_on_batch "
-                                      "covers a model that holds it")
+        training = getattr(_trace, "training_graph", False)
+        if training and not energy.layer.trainable:
+            raise NotImplementedError("this DescriptorMLP is not trainable: neither tfcompute(train=True) nor train_on_batch "
+                                      "covers a model that holds it (construct it with trainable=True)")
         out = energy.layer.forces(nl.tensor, virial)
-        _trace_log().append({"op": "descriptor_mlp"})   # (no plan: a model calling it keeps the eager path)
+        entry = {"op": "descriptor_mlp"}   # (no plan: a model calling it keeps the eager path)
+        if training:
+            # what tfcompute's training step needs (no "potential": the layer's own sweep trains it, DescriptorMLP.loss_gradient)
+            entry.update(layer=energy.layer, nlist=nl, forces=out[0] if virial else out)
+        _trace_log().append(entry)
         return out
     if isinstance(energy, BiasedEnergy):
         if virial:

@@ -408,6 +408,27 @@ class tfcompute:
             layer.after_update()  # pair-MLP: operand images <- theta, on the device
         self._train_potential = pot  # keep alive until the stream has consumed it
 
+    def _train_descriptor(self, nlist_t, offset, n, entry):
+        """train_on_batch for a model whose forces are one trainable DescriptorMLP: loss and weight gradient in one sweep over
+        the batch's pair vectors (DescriptorMLP.loss_gradient, with the forces the model has just evaluated as the prediction),
+        optimizer step on the layer's flat weights on the device."""
+        domain = getattr(self._nlist, "domain", None)
+        if domain is not None and domain.world > 1:
+            raise NotImplementedError("training a DescriptorMLP over several ranks is not implemented")
+        m, layer = self.model, entry["layer"]
+        theta = layer.w
+        if self._opt_state is None:
+            self._opt_state = torch.zeros(ops.optimizer_state_floats(int(theta.numel())), dtype=torch.float32,
+                                          device=self.system.device)
+            if m.metrics:
+                m.metrics[0].state = self._opt_state
+        if getattr(self, "_opt_desc", None) is None:
+            self._opt_desc = m.optimizer.desc(layer.nonneg_mask, layer.l1_reg)
+        pred = entry["forces"]
+        accum = layer.loss_gradient(nlist_t, self._labels[offset:offset + n],
+                                    pred=pred if pred.dtype == torch.float32 else pred.to(torch.float32))
+        ops.optimizer_step(theta, accum, 1.0 / (4.0 * float(n)), self._opt_state, self._opt_desc)
+
     def _maybe_install_train_plan(self, nbatch):
         """A training step whose model is ONE trainable pair energy on the step's own neighbor tensor (LJLayer, WCARepulsion, PairMLP,
         a traced energy with weights) is, from the second step on, a fixed sequence -- pair vectors, training sweep (prediction, loss,
@@ -574,8 +595,15 @@ class tfcompute:
             else:
                 self.outputs = [np.append(o1, o2, axis=0) for o1, o2 in zip(self.outputs, extra)]
         if self.train:
+            desc = [e for e in simmodel._trace_log()[mark:] if e.get("op") == "descriptor_mlp" and e.get("layer") is not None]
             if any(e.get("op") == "generic" for e in simmodel._trace_log()[mark:]):
                 self._train_generic(output, offset, n)
+            elif desc:
+                # a trainable DescriptorMLP: its own sweep, eager every step (no training plan, _train_seen stays unset)
+                if (len(desc) != 1 or fused_entries or not desc[0].get("is_output") or desc[0]["nlist"].tensor is not nlist_t):
+                    raise ValueError('training a DescriptorMLP needs its compute_nlist_forces on the step\'s own neighbor list to be '
+                                     'the model\'s only forces and its first output')
+                self._train_descriptor(nlist_t, offset, n, desc[0])
             else:
                 self._train_on_batch(nlist_t, offset, n, fused_entries)
                 self._train_seen = (list(simmodel._trace_log()[mark:]), nlist_t, output)

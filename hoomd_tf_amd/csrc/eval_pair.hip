@@ -397,7 +397,9 @@ __global__ __launch_bounds__(256) void bias_combine_kernel(V *__restrict__ force
     f.x += alpha * b.x;
     f.y += alpha * b.y;
     f.z += alpha * b.z;
-    f.w += alpha * cv; // rank-0 energy term tiled into every particle (simmodel.py:567-572)
+    // rank-0 energy term tiled into every particle (simmodel.py:567-572); the product in the force's own precision, like the
+    // three above it (alpha * cv between two floats would be rounded to fp32 before it meets a double energy)
+    f.w += alpha * (decltype(f.w))cv;
     force[i] = f;
 }
 

@@ -49,15 +49,25 @@ __global__ __launch_bounds__(256) void rdf_hist_kernel(const typename Vec4<IT>::
         if (sh[i]) atomicAdd(&hist[i], sh[i]);
 }
 
+__device__ __forceinline__ float rdf_shell_edge(unsigned i, unsigned nbins, float r0, float r1) {
+#pragma clang fp contract(off)
+    const float step = (r1 - r0) / (float)nbins;
+    const float off = (float)i * step;
+    return i == nbins ? r1 : off + r0;
+}
+
 __global__ void rdf_finalize_kernel(const unsigned *__restrict__ hist, unsigned nbins, float r0, float r1,
                                     float *__restrict__ rdf, float *__restrict__ rs) {
     unsigned b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nbins) return;
-    // shell = linspace(r0, r1, nbins + 1) evaluated in double then rounded to fp32 (as numpy does)
-    const double step = ((double)r1 - (double)r0) / (double)nbins;
-    const float lo = (float)((double)r0 + b * step);
-    const float hi = (b + 1 == nbins) ? r1 : (float)((double)r0 + (b + 1) * step);
-    const float vol = hi * hi * hi - lo * lo * lo;
+    // shell = tf.linspace(r0, r1, nbins + 1) on the fp32 r_range (simmodel.py:657, :664): start + step * i with step =
+    // (r1 - r0) / nbins, every operation rounded to fp32 on its own, the last edge r1 itself (NumPy's linspace of two
+    // float32 scalars does the same).  Evaluated in double and rounded once, an edge lands an ulp away from that now and
+    // then -- which a shell 1/2046 of the range wide sees as 5e-4 of its volume.
+    const float lo = rdf_shell_edge(b, nbins, r0, r1), hi = rdf_shell_edge(b + 1, nbins, r0, r1);
+    // hi^3 - lo^3 cancels: each cube rounded ONCE (an fp32 product chain rounds twice, and a contracted one differently for
+    // the two cubes), the difference and the quotient in fp32 as the reference takes them
+    const float vol = (float)((double)hi * hi * hi) - (float)((double)lo * lo * lo);
     rdf[b] = (float)hist[b + 1] / vol;
     rs[b] = (hi + lo) * 0.5f;
 }

@@ -205,8 +205,9 @@ __global__ __launch_bounds__(256) void topk_values_kernel(const float *__restric
 #pragma unroll
         for (int t = 0; t < kTopSlots; ++t) {
             if (!taken[t]) {
-                // order-preserving map of a float onto unsigned: flip the sign bit, or all bits of a negative
-                unsigned u = __float_as_uint(v[t]);
+                // order-preserving map of a float onto unsigned: flip the sign bit, or all bits of a negative.  -0.0 EQUALS
+                // +0.0 (top_k: the lower index first), so both take +0.0's key; the value written out keeps its own bits
+                unsigned u = v[t] == 0.0f ? 0u : __float_as_uint(v[t]);
                 u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
                 const unsigned long long key = ((unsigned long long)u << 32) | (0xFFFFFFFFu - ((unsigned)(t * 64) + lane));
                 if (!have || key > best) best = key;

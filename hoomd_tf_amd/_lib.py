@@ -276,6 +276,15 @@ DESC_TRAIN_PROTOTYPES = {
     "htf_dtrain_loss_grad": (_i, [_vp, _i, _u, _u, _u, _u, _u, _u, _i, _vp, _vp, C.c_float, _vp, _i, _vp, _vp, _vp, _vp]),
 }
 
+# the descriptor network with a cutoff and over a row list (include/htf_bp.h; DescriptorMLP(r_cut=..., n_species=...)): the two
+# tables above with (rows, n_rows, r_cut) before the stream, the descriptor entry with r_cut alone
+BP_PROTOTYPES = {
+    "htf_bp_forces": (_i, [_vp, _i, _u, _u, _u, _u, _u, _u, _i, _vp, _vp, C.c_float, _vp, _i, _vp, _vp, _u, C.c_float, _vp]),
+    "htf_bp_descriptor": (_i, [_vp, _i, _u, _u, _u, _u, _vp, C.c_float, _vp, _i, C.c_float, _vp]),
+    "htf_bp_scratch_floats": (_sz, [_u, _u, _u, _u, _u]),
+    "htf_bp_loss_grad": (_i, [_vp, _i, _u, _u, _u, _u, _u, _u, _i, _vp, _vp, C.c_float, _vp, _i, _vp, _vp, _vp, _vp, _u, C.c_float, _vp]),
+}
+
 
 ABI_VERSION = 5  # include/htf_amd.h HTF_AMD_ABI_VERSION: the struct layouts the ctypes Structures of this file mirror
 
@@ -288,7 +297,8 @@ def _load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(PROTOTYPES.items()) + list(STANDIN_PROTOTYPES.items()) + list(CG_PROTOTYPES.items())
                               + list(GEOM_PROTOTYPES.items()) + list(NLIST_PROTOTYPES.items())
-                              + list(DESC_PROTOTYPES.items()) + list(DESC_TRAIN_PROTOTYPES.items())):
+                              + list(DESC_PROTOTYPES.items()) + list(DESC_TRAIN_PROTOTYPES.items())
+                              + list(BP_PROTOTYPES.items())):
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -334,7 +344,8 @@ class _PybindLib:
         self._mod = mod
         for name, (res, args) in (list(PROTOTYPES.items()) + list(STANDIN_PROTOTYPES.items()) + list(CG_PROTOTYPES.items())
                                   + list(GEOM_PROTOTYPES.items()) + list(NLIST_PROTOTYPES.items())
-                                  + list(DESC_PROTOTYPES.items()) + list(DESC_TRAIN_PROTOTYPES.items())):
+                                  + list(DESC_PROTOTYPES.items()) + list(DESC_TRAIN_PROTOTYPES.items())
+                                  + list(BP_PROTOTYPES.items())):
             fn = getattr(mod, name)  # AttributeError if the module lacks a declared symbol
             ptr_at = tuple(i for i, t in enumerate(args) if _is_pointer(t))
             setattr(self, name, self._wrap(fn, ptr_at, res is _vp))

@@ -1,0 +1,142 @@
+// The descriptor network with a smooth cutoff and over a row list (include/htf_bp.h, htf.DescriptorMLP(r_cut=..., n_species=...)).
+//
+// The row bodies are desc_row.h's and dtrain_row.h's, instantiated here with the row list on and the cutoff on or off, so a
+// row evaluated here without a cutoff carries the bits desc_mlp.hip and desc_train.hip give it.  One network per species is
+// one launch per species: Python partitions the batch into ascending row lists and passes each with its species' weights.
+// Every output row is written by the one launch that lists it: no memset, no atomics.  The sweep's partials are a function
+// of n_rows alone and desc_train.hip's reduction adds them, so entry q of the list is row q of a batch of n_rows, bit for bit.
+// Built with -ffp-contract=on like desc_mlp.o and desc_train.o (csrc/Makefile).
+#include "htf_bp.h"
+#include "desc_row.h"
+#include "dtrain_row.h"
+
+namespace htf {
+namespace {
+
+template <bool FORCES, bool TANH, bool VIRIAL, bool CUT, typename IT>
+__global__ __launch_bounds__(256) void bp_rows_kernel(const typename Vec4<IT>::type *__restrict__ nlist, const int *__restrict__ rows,
+                                                      unsigned n, unsigned NN, const float *__restrict__ weights,
+                                                      const float *__restrict__ mu, int K, int T, int H1, int H2, float gap, float rc,
+                                                      void *__restrict__ out, int out_f64, void *__restrict__ virial9) {
+    desc_rows<FORCES, TANH, VIRIAL, CUT, true, IT>(nlist, rows, n, NN, weights, mu, K, T, H1, H2, gap, rc, out, out_f64, virial9);
+}
+
+template <bool TANH, bool CUT, typename IT>
+__global__ __launch_bounds__(256, 1) void bp_sweep_kernel(const typename Vec4<IT>::type *__restrict__ nlist, const int *__restrict__ rows,
+                                                          unsigned n, unsigned NN, const float *__restrict__ weights,
+                                                          const float *__restrict__ mu, int K, int T, int H1, int H2, float gap, float rc,
+                                                          const void *__restrict__ labels, int labels_f64,
+                                                          const float4 *__restrict__ pred, float *__restrict__ partials) {
+    dtrain_rows<TANH, CUT, true, IT>(nlist, rows, n, NN, weights, mu, K, T, H1, H2, gap, rc, labels, labels_f64, pred, partials);
+}
+
+int bp_check(unsigned B, unsigned n_rows, float r_cut) {
+    HTF_REQUIRE(n_rows <= B, "descriptor network: n_rows %u > B %u", n_rows, B);
+    HTF_REQUIRE(r_cut >= 0.0f && r_cut <= 3.402823466e+38f, "descriptor network: r_cut = %g must be finite and positive, or 0 for none",
+                (double)r_cut);
+    return HTF_OK;
+}
+
+} // namespace
+} // namespace htf
+
+extern "C" int htf_bp_forces(const void *d_nlist, int nlist_dtype, unsigned B, unsigned NN, unsigned K, unsigned n_types, unsigned H1,
+                             unsigned H2, int activation, const float *d_weights, const float *d_mu, float gap, void *d_force,
+                             int force_dtype, void *d_virial9, const int *d_rows, unsigned n_rows, float r_cut, htf_stream stream) {
+    using namespace htf;
+    int rc = desc_check(d_nlist, nlist_dtype, B, NN, K, n_types, d_mu, gap, d_force, force_dtype);
+    if (rc != HTF_OK) return rc;
+    if ((rc = desc_check_network(d_weights, H1, H2, activation)) != HTF_OK) return rc;
+    if ((rc = bp_check(B, n_rows, r_cut)) != HTF_OK) return rc;
+    if (n_rows == 0) return HTF_OK;
+    const size_t lds = desc_lds_forces(K, n_types, H1, H2);
+    const int out_f64 = force_dtype == HTF_F64;
+    const hipStream_t s = (hipStream_t)stream;
+#define HTF_BK(TANH, VIR, CUT, T, V4)                                                                                             \
+    hipLaunchKernelGGL((bp_rows_kernel<true, TANH, VIR, CUT, T>), dim3(desc_grid(n_rows)), dim3(256), lds, s, (const V4 *)d_nlist, \
+                       d_rows, n_rows, NN, d_weights, d_mu, (int)K, (int)n_types, (int)H1, (int)H2, gap, r_cut, d_force, out_f64, \
+                       d_virial9)
+#define HTF_BK2(TANH, VIR, CUT)                                                                                                   \
+    do {                                                                                                                          \
+        if (nlist_dtype == HTF_F32) HTF_BK(TANH, VIR, CUT, float, float4); else HTF_BK(TANH, VIR, CUT, double, double4);          \
+    } while (0)
+#define HTF_BK3(TANH, VIR)                                                                                                        \
+    do {                                                                                                                          \
+        if (r_cut > 0.0f) HTF_BK2(TANH, VIR, true); else HTF_BK2(TANH, VIR, false);                                               \
+    } while (0)
+    if (activation == HTF_ACT_TANH) {
+        if (d_virial9) HTF_BK3(true, true); else HTF_BK3(true, false);
+    } else {
+        if (d_virial9) HTF_BK3(false, true); else HTF_BK3(false, false);
+    }
+#undef HTF_BK3
+#undef HTF_BK2
+#undef HTF_BK
+    return check_launch("bp_rows_kernel");
+}
+
+extern "C" int htf_bp_descriptor(const void *d_nlist, int nlist_dtype, unsigned B, unsigned NN, unsigned K, unsigned n_types,
+                                 const float *d_mu, float gap, void *d_out, int out_dtype, float r_cut, htf_stream stream) {
+    using namespace htf;
+    int rc = desc_check(d_nlist, nlist_dtype, B, NN, K, n_types, d_mu, gap, d_out, out_dtype);
+    if (rc != HTF_OK) return rc;
+    if ((rc = bp_check(B, B, r_cut)) != HTF_OK) return rc;
+    if (B == 0) return HTF_OK;
+    const size_t lds = desc_lds_descriptor(K);
+    const int out_f64 = out_dtype == HTF_F64;
+    const hipStream_t s = (hipStream_t)stream;
+#define HTF_BG(CUT, T, V4)                                                                                                        \
+    hipLaunchKernelGGL((bp_rows_kernel<false, false, false, CUT, T>), dim3(desc_grid(B)), dim3(256), lds, s, (const V4 *)d_nlist,  \
+                       (const int *)nullptr, B, NN, (const float *)nullptr, d_mu, (int)K, (int)n_types, 0, 0, gap, r_cut, d_out,   \
+                       out_f64, nullptr)
+    if (r_cut > 0.0f) {
+        if (nlist_dtype == HTF_F32) HTF_BG(true, float, float4); else HTF_BG(true, double, double4);
+    } else {
+        if (nlist_dtype == HTF_F32) HTF_BG(false, float, float4); else HTF_BG(false, double, double4);
+    }
+#undef HTF_BG
+    return check_launch("bp_rows_kernel");
+}
+
+extern "C" size_t htf_bp_scratch_floats(unsigned n_rows, unsigned K, unsigned n_types, unsigned H1, unsigned H2) {
+    using namespace htf;
+    if (dtrain_check(K, n_types, H1, H2) != HTF_OK) return 0;
+    return (size_t)dtrain_grid(n_rows) * (1 + (size_t)dtrain_params(K * n_types, H1, H2));
+}
+
+extern "C" int htf_bp_loss_grad(const void *d_nlist, int nlist_dtype, unsigned B, unsigned NN, unsigned K, unsigned n_types, unsigned H1,
+                                unsigned H2, int activation, const float *d_weights, const float *d_mu, float gap, const void *d_labels,
+                                int labels_dtype, const float *d_pred, float *d_accum, float *d_scratch, const int *d_rows,
+                                unsigned n_rows, float r_cut, htf_stream stream) {
+    using namespace htf;
+    int rc = dtrain_check_call(d_nlist, nlist_dtype, B, NN, K, n_types, H1, H2, activation, d_weights, d_mu, gap, d_labels, labels_dtype,
+                               d_pred, d_accum, d_scratch);
+    if (rc != HTF_OK) return rc;
+    if ((rc = bp_check(B, n_rows, r_cut)) != HTF_OK) return rc;
+    if (!d_accum) return HTF_OK;   // (B = 0 and nothing to zero-fill: no launch)
+    const unsigned n = 1u + dtrain_params(K * n_types, H1, H2);
+    const unsigned grid = dtrain_grid(n_rows);   // (0 for no rows: the reduction alone then writes zeros)
+    const hipStream_t s = (hipStream_t)stream;
+    if (grid) {
+        const size_t lds = dtrain_lds(K, n_types, H1, H2);
+        const int l64 = labels_dtype == HTF_F64;
+#define HTF_BT(TANH, CUT, T, V4)                                                                                                  \
+    hipLaunchKernelGGL((bp_sweep_kernel<TANH, CUT, T>), dim3(grid), dim3(256), lds, s, (const V4 *)d_nlist, d_rows, n_rows, NN,    \
+                       d_weights, d_mu, (int)K, (int)n_types, (int)H1, (int)H2, gap, r_cut, d_labels, l64, (const float4 *)d_pred, \
+                       d_scratch)
+#define HTF_BT2(TANH, CUT)                                                                                                        \
+    do {                                                                                                                          \
+        if (nlist_dtype == HTF_F32) HTF_BT(TANH, CUT, float, float4); else HTF_BT(TANH, CUT, double, double4);                    \
+    } while (0)
+        if (activation == HTF_ACT_TANH) {
+            if (r_cut > 0.0f) HTF_BT2(true, true); else HTF_BT2(true, false);
+        } else {
+            if (r_cut > 0.0f) HTF_BT2(false, true); else HTF_BT2(false, false);
+        }
+#undef HTF_BT2
+#undef HTF_BT
+        const int rl = check_launch("bp_sweep_kernel");
+        if (rl != HTF_OK) return rl;
+    }
+    return dtrain_reduce_launch(d_scratch, grid, n, d_accum, s);
+}

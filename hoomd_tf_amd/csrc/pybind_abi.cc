@@ -19,6 +19,7 @@
 #include "htf_nlist.h"
 #include "htf_desc.h"
 #include "htf_desc_train.h"
+#include "htf_bp.h"
 
 namespace py = pybind11;
 
@@ -184,6 +185,13 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
     X(htf_dtrain_scratch_floats) \
     X(htf_dtrain_loss_grad)
 
+// include/htf_bp.h: the descriptor network with a cutoff and over a row list (_lib.BP_PROTOTYPES)
+#define HTF_BP_FUNCTIONS(X) \
+    X(htf_bp_forces) \
+    X(htf_bp_descriptor) \
+    X(htf_bp_scratch_floats) \
+    X(htf_bp_loss_grad)
+
 PYBIND11_MODULE(_htf_abi, m) {
     m.doc() = "pybind11 binding of libhtf_amd.so's C ABI: pointers as integers";
     // a stale module (or library): this module's templates were instantiated from one header, the library it resolved at load
@@ -199,5 +207,6 @@ PYBIND11_MODULE(_htf_abi, m) {
     HTF_NLIST_FUNCTIONS(X)
     HTF_DESC_FUNCTIONS(X)
     HTF_DESC_TRAIN_FUNCTIONS(X)
+    HTF_BP_FUNCTIONS(X)
 #undef X
 }

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, ops, simmodel
+from . import _lib, cgmap, ops, simmodel
 from ._lib import lib, check
 from .initializers import mlp_params
 
@@ -307,6 +307,16 @@ class DescriptorMLP:
     ``w`` take effect at the next call.  The energy takes no part in arithmetic with other energies (it raises): evaluate
     each term with its own ``compute_nlist_forces`` and add the forces.
 
+    ``r_cut=rc`` multiplies every Gaussian by the cosine cutoff ``fc(r) = 0.5 (cos(pi r / rc) + 1)`` for ``r < rc`` and 0
+    beyond (include/htf_bp.h), so that a neighbor entering or leaving at ``rc`` changes neither energy nor force; ``rc``
+    (rounded to fp32) should not exceed the ``r_cut`` of the neighbor list, which is not checked.  ``None``: no cutoff.
+    ``n_species=S`` keeps one network per particle species, Behler-Parrinello's one network per element: ``w`` holds S
+    networks of P floats, network ``s`` at ``w[s P:(s + 1) P]`` initialised from ``mlp_params(seed + s, ...)``, and row ``i`` is
+    evaluated by network ``rint(species_i)``.  The species come with the call -- ``layer(nlist, positions)`` (column 3 of a
+    [B, 4] tensor, or a [B] tensor), ``forces(x, species=...)``, ``loss_gradient(x, labels, species=...)`` -- and a value
+    outside ``[0, S)`` raises; with ``S = 1`` they are ignored.  Each call partitions the rows by species on the device
+    (one read-back of the S counts, cached while the same species tensor is passed) and launches once per species present.
+
     ``trainable=True`` makes the layer learn by force matching (include/htf_desc_train.h): under ``tfcompute.attach(...,
     train=True)`` every batch is one ``loss_gradient`` sweep -- the sum of squared residuals of (F_i, E_i) against the
     labels and its gradient with respect to ``w``, one pass over the pair vectors -- and one optimizer step on ``w``, on
@@ -322,9 +332,16 @@ class DescriptorMLP:
     l1_reg = (0.0,)
 
     def __init__(self, K=16, H1=32, H2=32, low=0.0, high=3.0, n_types=1, activation="tanh", seed=3, device=None,
-                 trainable=False):
-        K, H1, H2, n_types = int(K), int(H1), int(H2), int(n_types)
+                 trainable=False, r_cut=None, n_species=1):
+        K, H1, H2, n_types, n_species = int(K), int(H1), int(H2), int(n_types), int(n_species)
         self.trainable = bool(trainable)
+        if r_cut is not None:
+            r_cut = float(np.float32(r_cut))
+            if not (np.isfinite(r_cut) and r_cut > 0):
+                raise ValueError("DescriptorMLP: r_cut = %r must be finite and positive (None: no cutoff)" % (r_cut,))
+        if n_species < 1:
+            raise ValueError("DescriptorMLP: n_species = %d; at least one network" % n_species)
+        self.r_cut, self.n_species = r_cut, n_species
         activation = activation or "linear"
         if activation not in ("tanh", "linear"):
             raise ValueError("DescriptorMLP: activation must be 'tanh' or 'linear', not %r" % (activation,))
@@ -342,9 +359,10 @@ class DescriptorMLP:
         self.D = n_types * K
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
-        p = mlp_params(seed=seed, K=self.D, H1=H1, H2=H2)
-        self._shapes = [p[k].shape for k in self._KEYS]
-        self.w = torch.tensor(np.concatenate([p[k].ravel() for k in self._KEYS]), dtype=torch.float32, device=device)
+        ps = [mlp_params(seed=seed + s, K=self.D, H1=H1, H2=H2) for s in range(n_species)]
+        self._shapes = [ps[0][k].shape for k in self._KEYS]
+        self.P = sum(int(np.prod(sh)) for sh in self._shapes)   # floats of one network
+        self.w = torch.tensor(np.concatenate([p[k].ravel() for p in ps for k in self._KEYS]), dtype=torch.float32, device=device)
         self.mu = torch.tensor(self.centers, dtype=torch.float32, device=device)
 
     def get_config(self):
@@ -352,24 +370,33 @@ class DescriptorMLP:
                'activation': self.activation}
         if self.trainable:
             cfg['trainable'] = True
+        if self.r_cut is not None:
+            cfg['r_cut'] = self.r_cut
+        if self.n_species != 1:
+            cfg['n_species'] = self.n_species
         return cfg
 
     def get_weights(self):
-        flat, out, o = self.w.detach().cpu().numpy(), [], 0
+        """The six Keras arrays; with ``n_species = S > 1`` each has a leading axis of length S."""
+        S = self.n_species
+        flat, out, o = self.w.detach().cpu().numpy().reshape(S, self.P), [], 0
         for shape in self._shapes:
             n = int(np.prod(shape))
-            out.append(flat[o:o + n].reshape(shape).copy())
+            a = flat[:, o:o + n].reshape((S,) + tuple(shape)).copy()
+            out.append(a if S > 1 else a[0])
             o += n
         return out
 
     def set_weights(self, ws):
         ws = list(ws)
+        S = self.n_species
         if len(ws) != len(self._KEYS):
             raise ValueError("DescriptorMLP: expected %d weight arrays, got %d" % (len(self._KEYS), len(ws)))
         for k, shape, w in zip(self._KEYS, self._shapes, ws):
+            shape = ((S,) if S > 1 else ()) + tuple(shape)
             if np.shape(w) != shape:
                 raise ValueError("DescriptorMLP: shape mismatch for %s: %r, expected %r" % (k, np.shape(w), shape))
-        flat = np.concatenate([np.asarray(w, dtype=np.float32).ravel() for w in ws])
+        flat = np.concatenate([np.asarray(w, dtype=np.float32).reshape(S, -1) for w in ws], axis=1).ravel()
         with torch.no_grad():
             self.w.copy_(torch.from_numpy(flat))   # (in place: the next call reads it)
 
@@ -388,52 +415,122 @@ class DescriptorMLP:
         if x.shape[1] > self.MAX_NN:
             raise ValueError("DescriptorMLP: NN = %d neighbor slots; the kernel takes at most %d" % (x.shape[1], self.MAX_NN))
         ops._dev(self.w, "DescriptorMLP.w", torch.float32)
-        if self.w.device != x.device or self.w.numel() != sum(int(np.prod(s)) for s in self._shapes):
+        if self.w.device != x.device or self.w.numel() != self.n_species * self.P:
             raise ValueError("DescriptorMLP: the weights (%d floats on %s) do not fit a call on %s" % (self.w.numel(), self.w.device, x.device))
         return int(x.shape[0]), int(x.shape[1])
 
-    def forces(self, x, virial=False):
+    def _partition(self, species, x):
+        """The rows of a batch grouped by species: (rows, counts) -- ``rows`` int32 [B] on the device, species 0's rows first,
+        ascending inside a species (a stable sort of the rounded species); ``counts`` the S sizes on the host.  One read-back
+        of the counts serves the launch sizes and the range check.  Cached while the same species tensor is passed."""
+        S, B = self.n_species, int(x.shape[0])
+        if species is None:
+            raise ValueError("DescriptorMLP: n_species = %d needs the particles' species: layer(nlist, positions), "
+                             "forces(x, species=...) or loss_gradient(x, labels, species=...)" % S)
+        if (not isinstance(species, torch.Tensor) or species.device != x.device
+                or tuple(species.shape) not in ((B,), (B, 4))):
+            raise ValueError("DescriptorMLP: species must be a [%d] or [%d, 4] tensor on %s, got %s" % (
+                B, B, x.device, tuple(species.shape) if isinstance(species, torch.Tensor) else type(species)))
+
+        def build():
+            col = species[:, 3] if species.dim() == 2 else species
+            sp = torch.round(col.detach().to(torch.float64))
+            idx = torch.where((sp >= 0) & (sp < S), sp, torch.full_like(sp, S)).to(torch.int64)   # (NaN: S, out of range)
+            rows = torch.argsort(idx, stable=True).to(torch.int32).contiguous()
+            return rows, torch.bincount(idx, minlength=S + 1).cpu().tolist()
+
+        rows, counts = cgmap._cached("descriptor-species", (species,), x.device, build, extra=S)
+        if counts[S]:
+            raise ValueError("DescriptorMLP: %d of %d rows have a species outside [0, %d)" % (counts[S], B, S))
+        return rows, counts[:S]
+
+    def species_counts(self, species, x):
+        """Rows per species of the batch ``x`` (the cached partition's counts); [B] for one species."""
+        return [int(x.shape[0])] if self.n_species == 1 else self._partition(species, x)[1]
+
+    def _launches(self, species, x):
+        """One (species, row-list pointer, rows, weight pointer) per launch: the whole batch for one network, else one per
+        species present, each with its slice of the partition and of ``w``."""
+        if self.n_species == 1:
+            return [(0, None, int(x.shape[0]), self.w.data_ptr())], None
+        rows, counts = self._partition(species, x)
+        out, o = [], 0
+        for s, c in enumerate(counts):
+            if c:
+                out.append((s, rows.data_ptr() + 4 * o, c, self.w.data_ptr() + 4 * s * self.P))
+            o += c
+        return out, rows   # (rows: kept alive by the caller until its launches are queued)
+
+    def forces(self, x, virial=False, species=None):
         """The kernel on a pair-vector tensor ``x`` [B, NN, 4] (fp32 or fp64): forces [B, 4] in ``x``'s dtype, and the
-        [B, 3, 3] virial when ``virial``.  compute_nlist_forces calls this for the layer's energy."""
+        [B, 3, 3] virial when ``virial``.  compute_nlist_forces calls this for the layer's energy.  ``species``: [B] or
+        [B, 4] (column 3), needed when ``n_species > 1``."""
         B, NN = self._check(x)
         out = torch.empty((B, 4), dtype=x.dtype, device=x.device)
         v = torch.empty((B, 3, 3), dtype=x.dtype, device=x.device) if virial else None
         act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
-        check(lib.htf_desc_forces(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, self.w.data_ptr(),
-                                  self.mu.data_ptr(), float(self.gap), out.data_ptr(), ops._dt(out),
-                                  v.data_ptr() if v is not None else None, ops._stream(x)))
+        if self.r_cut is None and self.n_species == 1:
+            check(lib.htf_desc_forces(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, self.w.data_ptr(),
+                                      self.mu.data_ptr(), float(self.gap), out.data_ptr(), ops._dt(out),
+                                      v.data_ptr() if v is not None else None, ops._stream(x)))
+            return (out, v) if virial else out
+        launches, rows = self._launches(species, x)
+        for _, d_rows, n_rows, d_w in launches:   # every row is in exactly one list: no memset
+            check(lib.htf_bp_forces(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, d_w,
+                                    self.mu.data_ptr(), float(self.gap), out.data_ptr(), ops._dt(out),
+                                    v.data_ptr() if v is not None else None, d_rows, n_rows, float(self.r_cut or 0.0),
+                                    ops._stream(x)))
         return (out, v) if virial else out
 
-    def loss_gradient(self, x, labels, pred=None, accum=None):
+    def loss_gradient(self, x, labels, pred=None, accum=None, species=None):
         """One force-matching sweep (htf_dtrain_loss_grad) over a pair-vector tensor ``x`` [B, NN, 4] (fp32 or fp64) and
         ``labels`` [B, 4] (fp32 or fp64): returns ``accum`` [1 + P] fp32 on the device, {sum of squared residuals of
         (F_i, E_i), its gradient with respect to ``w``} -- what ``ops.optimizer_step(w, accum, 1 / (4 B), ...)`` consumes for
         Keras' MeanSquaredError.  ``pred`` [B, 4] fp32: the layer's ``forces(x)`` at the current weights, evaluated here
-        when not given.  Two calls on the same inputs give the same bits."""
+        when not given.  Two calls on the same inputs give the same bits.  With ``n_species = S > 1`` (``species`` as for
+        ``forces``) ``accum`` is [S, 1 + P]: row ``s`` holds the residuals and the gradient of network ``s`` over species
+        ``s``'s rows, zeros when it has none; each row steps its own slice of ``w``."""
         B, NN = self._check(x)
         ops._dev(labels, "labels")
         ops._dt(labels)
         if tuple(labels.shape) != (B, 4) or labels.device != x.device:
             raise ValueError("DescriptorMLP: labels must be [%d, 4] on %s, got %s on %s" % (B, x.device, tuple(labels.shape), labels.device))
         if pred is None:
-            pred = self.forces(x)
+            pred = self.forces(x, species=species)
             if pred.dtype != torch.float32:
                 pred = pred.to(torch.float32)
         ops._dev(pred, "pred", torch.float32)
         if tuple(pred.shape) != (B, 4) or pred.device != x.device:
             raise ValueError("DescriptorMLP: pred must be [%d, 4] on %s, got %s on %s" % (B, x.device, tuple(pred.shape), pred.device))
-        P = int(self.w.numel())
+        S, P = self.n_species, self.P
         if accum is None:
-            accum = torch.empty(1 + P, dtype=torch.float32, device=x.device)
+            accum = torch.empty((S, 1 + P) if S > 1 else (1 + P,), dtype=torch.float32, device=x.device)
         ops._dev(accum, "accum", torch.float32)
-        if accum.numel() != 1 + P or accum.device != x.device:
-            raise ValueError("DescriptorMLP: accum must hold %d floats on %s" % (1 + P, x.device))
-        scratch = torch.empty(int(lib.htf_dtrain_scratch_floats(B, self.K, self.n_types, self.H1, self.H2)), dtype=torch.float32,
-                              device=x.device)
+        if accum.numel() != S * (1 + P) or accum.device != x.device:
+            raise ValueError("DescriptorMLP: accum must hold %d floats on %s" % (S * (1 + P), x.device))
         act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
-        check(lib.htf_dtrain_loss_grad(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, self.w.data_ptr(),
+        if self.r_cut is None and S == 1:
+            scratch = torch.empty(int(lib.htf_dtrain_scratch_floats(B, self.K, self.n_types, self.H1, self.H2)), dtype=torch.float32,
+                                  device=x.device)
+            check(lib.htf_dtrain_loss_grad(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, self.w.data_ptr(),
+                                           self.mu.data_ptr(), float(self.gap), labels.data_ptr(), ops._dt(labels), pred.data_ptr(),
+                                           accum.data_ptr(), scratch.data_ptr(), ops._stream(x)))
+            return accum
+        launches, rows = self._launches(species, x)
+        # one scratch buffer for the largest species: the launches run one after the other on the stream
+        scratch = torch.empty(max(1, int(lib.htf_bp_scratch_floats(max([n for _, _, n, _ in launches] or [0]), self.K, self.n_types,
+                                                                   self.H1, self.H2))), dtype=torch.float32, device=x.device)
+        present = set()
+        for s, d_rows, n_rows, d_w in launches:
+            present.add(s)
+            check(lib.htf_bp_loss_grad(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, d_w,
                                        self.mu.data_ptr(), float(self.gap), labels.data_ptr(), ops._dt(labels), pred.data_ptr(),
-                                       accum.data_ptr(), scratch.data_ptr(), ops._stream(x)))
+                                       accum.data_ptr() + 4 * s * (1 + P), scratch.data_ptr(), d_rows, n_rows,
+                                       float(self.r_cut or 0.0), ops._stream(x)))
+        if S > 1:
+            for s in range(S):
+                if s not in present:
+                    accum.view(S, 1 + P)[s].zero_()
         return accum
 
     def descriptor(self, nlist):
@@ -441,18 +538,24 @@ class DescriptorMLP:
         x = simmodel._as_nlist(nlist).tensor
         B, NN = self._check(x)
         out = torch.empty((B, self.D), dtype=x.dtype, device=x.device)
-        check(lib.htf_desc_descriptor(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.mu.data_ptr(), float(self.gap),
-                                      out.data_ptr(), ops._dt(out), ops._stream(x)))
+        if self.r_cut is None:
+            check(lib.htf_desc_descriptor(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.mu.data_ptr(), float(self.gap),
+                                          out.data_ptr(), ops._dt(out), ops._stream(x)))
+        else:
+            check(lib.htf_bp_descriptor(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.mu.data_ptr(), float(self.gap),
+                                        out.data_ptr(), ops._dt(out), float(self.r_cut), ops._stream(x)))
         simmodel._trace_log().append({"op": "descriptor"})   # (no replay: a model calling it keeps the eager path)
         return out
 
-    def __call__(self, nlist):
+    def __call__(self, nlist, positions=None):
         nl = simmodel._as_nlist(nlist)
         if len(nl.shape) != 3 or nl.shape[2] != 4:
             raise ValueError("DescriptorMLP: nlist must be [B, NN, 4], got %s" % (tuple(nl.shape),))
         if nl.shape[1] > self.MAX_NN:
             raise ValueError("DescriptorMLP: NN = %d neighbor slots; the kernel takes at most %d" % (nl.shape[1], self.MAX_NN))
-        return simmodel.DescriptorEnergy(nl, self)
+        if self.n_species > 1 and positions is None:
+            raise ValueError("DescriptorMLP: n_species = %d needs the particles' species: layer(nlist, positions)" % self.n_species)
+        return simmodel.DescriptorEnergy(nl, self, positions if self.n_species > 1 else None)
 
 
 class EDSLayer:

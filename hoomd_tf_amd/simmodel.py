@@ -1427,11 +1427,12 @@ class MLPEnergy(PairEnergy):
 class DescriptorEnergy(PairEnergy):
     """DescriptorMLP(nlist): the per-particle energy [N] of the descriptor network.  compute_nlist_forces evaluates it in one
     kernel (htf_desc_forces) and keeps the step eager.  It does not combine with other energies: arithmetic raises, so a sum
-    the kernel cannot form never reaches the forces."""
+    the kernel cannot form never reaches the forces.  ``species``: the tensor the layer reads the particles' own species from
+    (one network per species, DescriptorMLP(n_species=...)), None for a layer of one network."""
     reduced = True
 
-    def __init__(self, nlist, layer):
-        self.nlist, self.layer = nlist, layer
+    def __init__(self, nlist, layer, species=None):
+        self.nlist, self.layer, self.species = nlist, layer, species
 
     def key(self):
         return ("descriptor-mlp",)
@@ -1441,7 +1442,7 @@ class DescriptorEnergy(PairEnergy):
 
     def tensor(self):
         _trace_log().append({"op": "eager_value"})
-        return self.layer.forces(self.nlist.tensor)[:, 3].clone()
+        return self.layer.forces(self.nlist.tensor, species=self.species)[:, 3].clone()
 
     def _combine(self, *other):
         raise TypeError("DescriptorMLP's energy cannot be combined with other terms; call compute_nlist_forces on each "
@@ -1705,8 +1706,8 @@ def compute_nlist_forces(nlist, energy, virial=False):
         if training and not energy.layer.trainable:
             raise NotImplementedError("this DescriptorMLP is not trainable: neither tfcompute(train=True) nor train_on_batch "
                                       "covers a model that holds it (construct it with trainable=True)")
-        out = energy.layer.forces(nl.tensor, virial)
-        entry = {"op": "descriptor_mlp"}   # (no plan: a model calling it keeps the eager path)
+        out = energy.layer.forces(nl.tensor, virial, species=energy.species)
+        entry = {"op": "descriptor_mlp", "species": energy.species}   # (no plan: a model calling it keeps the eager path)
         if training:
             # what tfcompute's training step needs (no "potential": the layer's own sweep trains it, DescriptorMLP.loss_gradient)
             entry.update(layer=energy.layer, nlist=nl, forces=out[0] if virial else out)

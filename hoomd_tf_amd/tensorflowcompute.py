@@ -417,17 +417,42 @@ class tfcompute:
             raise NotImplementedError("training a DescriptorMLP over several ranks is not implemented")
         m, layer = self.model, entry["layer"]
         theta = layer.w
+        if getattr(self, "_opt_desc", None) is None:
+            self._opt_desc = m.optimizer.desc(layer.nonneg_mask, layer.l1_reg)
+        pred = entry["forces"]
+        pred = pred if pred.dtype == torch.float32 else pred.to(torch.float32)
+        S = getattr(layer, "n_species", 1)
+        if S > 1:
+            return self._train_descriptor_species(nlist_t, offset, n, layer, pred, entry.get("species"))
         if self._opt_state is None:
             self._opt_state = torch.zeros(ops.optimizer_state_floats(int(theta.numel())), dtype=torch.float32,
                                           device=self.system.device)
             if m.metrics:
                 m.metrics[0].state = self._opt_state
-        if getattr(self, "_opt_desc", None) is None:
-            self._opt_desc = m.optimizer.desc(layer.nonneg_mask, layer.l1_reg)
-        pred = entry["forces"]
-        accum = layer.loss_gradient(nlist_t, self._labels[offset:offset + n],
-                                    pred=pred if pred.dtype == torch.float32 else pred.to(torch.float32))
+        accum = layer.loss_gradient(nlist_t, self._labels[offset:offset + n], pred=pred)
         ops.optimizer_step(theta, accum, 1.0 / (4.0 * float(n)), self._opt_state, self._opt_desc)
+
+    def _train_descriptor_species(self, nlist_t, offset, n, layer, pred, species):
+        """One network per species: one sweep for the batch, then one optimizer step per species present on that species'
+        slice of the weights, each with its own optimizer state and the scale 1 / (4 n) of the whole batch (the batch's mean
+        squared error is the sum of the species' shares).  A species without rows in the batch is not stepped: its weights and
+        its optimizer state stay as they are.  The reported loss is the sum of the species' sums of squared residuals / (4 n)."""
+        m, S, P = self.model, layer.n_species, layer.P
+        if getattr(self, "_opt_states", None) is None:
+            self._opt_states = [torch.zeros(ops.optimizer_state_floats(P), dtype=torch.float32, device=self.system.device)
+                                for _ in range(S)]
+            self._opt_state = torch.zeros(_lib.OPT_STATE_FLOATS, dtype=torch.float32, device=self.system.device)  # the metric's
+            if m.metrics:
+                m.metrics[0].state = self._opt_state
+        accum = layer.loss_gradient(nlist_t, self._labels[offset:offset + n], pred=pred, species=species)
+        scale = 1.0 / (4.0 * float(n))
+        for s, c in enumerate(layer.species_counts(species, nlist_t)):
+            if c:
+                ops.optimizer_step(layer.w[s * P:(s + 1) * P], accum[s], scale, self._opt_states[s], self._opt_desc)
+        loss = accum[:, 0].sum() * scale
+        self._opt_state[20] = loss      # (last loss, running sum and count: what the loss metric reads)
+        self._opt_state[18] += loss
+        self._opt_state[19] += 1.0
 
     def _maybe_install_train_plan(self, nbatch):
         """A training step whose model is ONE trainable pair energy on the step's own neighbor tensor (LJLayer, WCARepulsion, PairMLP,

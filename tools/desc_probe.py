@@ -4,9 +4,12 @@ For each shape: a random [N, NN, 4] fp32 pair-vector tensor (60..NN live neighbo
 the layer with K channels on [0, 3], H1 = H2 hidden units, tanh.  Timed: compute_nlist_forces(nlist, layer(nlist)) (the
 kernel), layer.descriptor(nlist) (its first stage), and compute_nlist_forces of the RBFExpansion -> masked sum -> Dense x 3
 energy under the same weights (torch ops + autograd, [N, NN, K] intermediates).  Device events around --iters calls per
-window, the median of --windows windows.  A torch route that runs out of device memory is reported as such.  One JSON line.
+window, the median of --windows windows (every window is listed too).  A torch route that runs out of device memory is
+reported as such.  --r-cut RC gives the layer the cosine cutoff, --species S one network per species with the rows split
+evenly (row i is species i mod S); the torch route is written for neither and is then left out, as with --no-torch.
+One JSON line.
 
-    python tools/desc_probe.py [--iters 10] [--windows 7]
+    python tools/desc_probe.py [--iters 10] [--windows 7] [--r-cut RC] [--species S] [--no-torch]
 """
 import argparse
 import json
@@ -35,7 +38,7 @@ def timed(fn, iters, windows):
         b.record()
         b.synchronize()
         out.append(a.elapsed_time(b) / iters)
-    return float(np.median(out))
+    return float(np.median(out)), [round(t, 4) for t in out]
 
 
 def pair_vectors(N, NN, dev, seed):
@@ -70,27 +73,49 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--windows", type=int, default=7)
+    ap.add_argument("--r-cut", type=float, default=None)
+    ap.add_argument("--species", type=int, default=1)
+    ap.add_argument("--no-torch", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("desc_probe: needs a GPU")
     dev = torch.device("cuda:0")
-    res = {"device": torch.cuda.get_device_name(0), "iters": a.iters, "windows": a.windows, "shapes": []}
+    res = {"device": torch.cuda.get_device_name(0), "iters": a.iters, "windows": a.windows, "r_cut": a.r_cut,
+           "species": a.species, "shapes": []}
+    extra = {}
+    if a.r_cut is not None:
+        extra["r_cut"] = a.r_cut
+    if a.species != 1:
+        extra["n_species"] = a.species
     for name, N, NN, K, T, H1, H2 in SHAPES:
         x = pair_vectors(N, NN, dev, seed=len(res["shapes"]) + 1)
-        lay = htf.DescriptorMLP(K=K, H1=H1, H2=H2, low=0.0, high=3.0, n_types=T, activation="tanh", seed=3)
+        lay = htf.DescriptorMLP(K=K, H1=H1, H2=H2, low=0.0, high=3.0, n_types=T, activation="tanh", seed=3, **extra)
         nl = htf.Nlist(x)
+        if a.species != 1:
+            pos = torch.zeros((N, 4), device=dev)
+            pos[:, 3] = (torch.arange(N, device=dev) % a.species).to(torch.float32)
+            energy = lambda: lay(nl, pos)   # noqa: E731
+        else:
+            energy = lambda: lay(nl)        # noqa: E731
         row = {"shape": name, "N": N, "NN": NN, "K": K, "n_types": T, "H1": H1, "H2": H2,
                "pair_tensor_MB": round(x.numel() * 4 / 1e6, 1)}
-        fk = htf.compute_nlist_forces(nl, lay(nl))
-        row["kernel_ms"] = round(timed(lambda: htf.compute_nlist_forces(nl, lay(nl)), a.iters, a.windows), 4)
-        row["descriptor_ms"] = round(timed(lambda: lay.descriptor(nl), a.iters, a.windows), 4)
+        fk = htf.compute_nlist_forces(nl, energy())
+        med, row["kernel_ms_windows"] = timed(lambda: htf.compute_nlist_forces(nl, energy()), a.iters, a.windows)
+        row["kernel_ms"] = round(med, 4)
+        row["descriptor_ms"] = round(timed(lambda: lay.descriptor(nl), a.iters, a.windows)[0], 4)
         row["kernel_read_TBps"] = round(x.numel() * 4 / (row["kernel_ms"] * 1e-3) / 1e12, 2)
+        if extra or a.no_torch:
+            htf.simmodel._trace_log().clear()
+            res["shapes"].append(row)
+            del x, fk, nl
+            torch.cuda.empty_cache()
+            continue
         run = layers_route(lay)
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
         try:
             ft = run(x)
-            row["torch_ms"] = round(timed(lambda: run(x), max(1, a.iters // 2), a.windows), 3)
+            row["torch_ms"] = round(timed(lambda: run(x), max(1, a.iters // 2), a.windows)[0], 3)
             row["torch_peak_GB"] = round(torch.cuda.max_memory_allocated() / 1e9, 2)
             scale = ft[:, :3].abs().max().item()
             row["max_force_diff_rel"] = float((fk[:, :3] - ft[:, :3]).abs().max().item() / scale)

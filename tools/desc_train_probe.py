@@ -2,6 +2,7 @@
 """Times the descriptor network's force-matching sweep at the C3 shape.
 
 Usage:  python tools/desc_train_probe.py [--n 131072] [--nn 128] [--iters 20] [--warmup 5] [--chunk 32768] [--json PATH]
+                                         [--r-cut RC] [--species S]
 
 N rows x NN slots, K = 32 channels, 64 x 64 tanh, one type.  HIP events around each launch, the median of --iters launches
 after --warmup:
@@ -11,6 +12,8 @@ after --warmup:
       three dense layers in plain torch (what RBFExpansion + Dense compute), forces by autograd with create_graph, the mean
       squared error over [N, 4], backward, one SGD step -- in row chunks of --chunk whose gradients add up, so that the
       [rows, NN, K] intermediates of the double backward fit whatever else shares the device.
+--r-cut RC gives the layer the cosine cutoff, --species S one network per species with the rows split evenly (row i is
+species i mod S); (c) is written for neither and is then left out.
 Prints one JSON line; (c)/(b) is the step a user gains over the torch route, optimizer kernel aside.  To see which kernels
 run: rocprofv3 --kernel-trace --stats -- python tools/desc_train_probe.py --only sweep
 """
@@ -50,6 +53,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=32768)
     ap.add_argument("--only", choices=["all", "sweep"], default="all")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--r-cut", type=float, default=None)
+    ap.add_argument("--species", type=int, default=1)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     N, NN, K = a.n, a.nn, 32
@@ -61,15 +66,22 @@ def main():
     mask = (torch.arange(NN, device=dev)[None, :] < cnt).to(torch.float32)[..., None]
     x = torch.cat([d * r * mask, torch.zeros((N, NN, 1), device=dev)], dim=2).contiguous()
     labels = 0.05 * torch.randn((N, 4), device=dev, generator=g)
-    lay = htf.DescriptorMLP(K=K, H1=64, H2=64, seed=9, trainable=True)
-    pred = lay.forces(x)
-    accum = torch.empty(1 + lay.w.numel(), dtype=torch.float32, device=dev)
+    extra, kw = {}, {}
+    if a.r_cut is not None:
+        extra["r_cut"] = a.r_cut
+    if a.species != 1:
+        extra["n_species"] = a.species
+        kw["species"] = (torch.arange(N, device=dev) % a.species).to(torch.float32)
+    lay = htf.DescriptorMLP(K=K, H1=64, H2=64, seed=9, trainable=True, **extra)
+    pred = lay.forces(x, **kw)
+    accum = torch.empty(a.species * (1 + lay.w.numel() // a.species), dtype=torch.float32, device=dev)
     out = {"shape": {"N": N, "NN": NN, "K": K, "H1": 64, "H2": 64, "activation": "tanh"}, "iters": a.iters, "warmup": a.warmup,
-           "device": torch.cuda.get_device_name(0)}
+           "r_cut": a.r_cut, "species": a.species, "device": torch.cuda.get_device_name(0)}
 
-    out["sweep_ms"] = timed(lambda: lay.loss_gradient(x, labels, pred=pred, accum=accum), a.iters, a.warmup)
+    out["sweep_ms"] = timed(lambda: lay.loss_gradient(x, labels, pred=pred, accum=accum, **kw), a.iters, a.warmup)
     if a.only == "all":
-        out["forces_ms"] = timed(lambda: lay.forces(x), a.iters, a.warmup)
+        out["forces_ms"] = timed(lambda: lay.forces(x, **kw), a.iters, a.warmup)
+    if a.only == "all" and not extra:
 
         W = [torch.nn.Parameter(torch.as_tensor(w, device=dev)) for w in lay.get_weights()]
         opt = torch.optim.SGD(W, lr=1e-4)

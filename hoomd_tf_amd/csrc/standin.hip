@@ -25,11 +25,12 @@ __global__ __launch_bounds__(256) void nve_step_kernel(typename Vec4<T>::type *_
     vel[i] = v;
 }
 
+// the largest squared displacement of a workgroup's (up to 1024) rows, in its thread 0 (s_max: 16 floats of LDS; ends behind a
+// barrier): the body max_disp_kernel and check_disp_kernel share, so that every form of the check decides on the same bits
 template <typename T>
-__global__ __launch_bounds__(1024) void max_disp_kernel(const typename Vec4<T>::type *__restrict__ pos,
-                                                        const typename Vec4<T>::type *__restrict__ ref, unsigned N,
-                                                        SBox<T> b, float *__restrict__ out) {
-    __shared__ float s_max[16];
+__device__ __forceinline__ float block_max_disp2(const typename Vec4<T>::type *__restrict__ pos,
+                                                 const typename Vec4<T>::type *__restrict__ ref, unsigned N, const SBox<T> &b,
+                                                 float *s_max) {
     unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
     float d2 = 0.f;
     if (i < N) {
@@ -47,11 +48,20 @@ __global__ __launch_bounds__(1024) void max_disp_kernel(const typename Vec4<T>::
     if (threadIdx.x < 16) {
         d2 = s_max[threadIdx.x];
         for (int m = 1; m < 16; m <<= 1) d2 = fmaxf(d2, __shfl_xor(d2, m));
-        // d2 >= 0: uint order == float order.  One atomic per 1024 particles (same-address
-        // atomics serialise at ~12 ns each: one per wave cost 25 us at N = 131072).
-        if (threadIdx.x == 0 && __float_as_uint(d2) > *(volatile unsigned *)out)
-            atomicMax((unsigned *)out, __float_as_uint(d2));
     }
+    return d2;
+}
+
+template <typename T>
+__global__ __launch_bounds__(1024) void max_disp_kernel(const typename Vec4<T>::type *__restrict__ pos,
+                                                        const typename Vec4<T>::type *__restrict__ ref, unsigned N,
+                                                        SBox<T> b, float *__restrict__ out) {
+    __shared__ float s_max[16];
+    const float d2 = block_max_disp2<T>(pos, ref, N, b, s_max);
+    // d2 >= 0: uint order == float order.  One atomic per 1024 particles (same-address
+    // atomics serialise at ~12 ns each: one per wave cost 25 us at N = 131072).
+    if (threadIdx.x == 0 && __float_as_uint(d2) > *(volatile unsigned *)out)
+        atomicMax((unsigned *)out, __float_as_uint(d2));
 }
 
 // The distance check of a replayed cycle in ONE launch (round 5: inside a hipGraph every dependent node costs >= 4.5 us, and
@@ -62,58 +72,47 @@ __global__ __launch_bounds__(1024) void max_disp_kernel(const typename Vec4<T>::
 // number last, behind a system-scope fence, so a host that sees cycle c sees everything that belongs to it -- where the captured
 // chain had a copy node each (a second stream forked inside the capture was worse: 29.6 -> 42 us per step, every kernel of a
 // multi-branch graph slower and 16-22 us at each fork).
-template <typename T>
+// CYCLE = false is the eager check step's form (htfs_check_rebuild_nlist): `out` is the ONE word the gate reads, there is no cycle
+// number and nothing goes to the host -- what is left is "zero the word, fill it" in one launch instead of two.
+template <typename T, bool CYCLE>
 __global__ __launch_bounds__(1024) void check_disp_kernel(const typename Vec4<T>::type *__restrict__ pos,
                                                           const typename Vec4<T>::type *__restrict__ ref, unsigned N,
                                                           SBox<T> b, unsigned *__restrict__ work, float *__restrict__ out,
                                                           float *__restrict__ h_out, htfs_mirror mirror) {
     __shared__ float s_max[16];
     __shared__ unsigned s_last;
-    unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-    float d2 = 0.f;
-    if (i < N) {
-        auto p = pos[i];
-        auto r = ref[i];
-        T dx = mimg<T>(p.x - r.x, b.L[0], b.Linv[0], b.periodic[0]);
-        T dy = mimg<T>(p.y - r.y, b.L[1], b.Linv[1], b.periodic[1]);
-        T dz = mimg<T>(p.z - r.z, b.L[2], b.Linv[2], b.periodic[2]);
-        d2 = (float)(dx * dx + dy * dy + dz * dz);
-        if (!(d2 == d2)) d2 = 0.f; // an inert row has not moved
-    }
-    for (int m = 1; m < 64; m <<= 1) d2 = fmaxf(d2, __shfl_xor(d2, m));
-    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = d2;
     if (threadIdx.x == 0) s_last = 0u;
-    __syncthreads();
-    if (threadIdx.x < 16) {
-        d2 = s_max[threadIdx.x];
-        for (int m = 1; m < 16; m <<= 1) d2 = fmaxf(d2, __shfl_xor(d2, m));
-        if (threadIdx.x == 0) {
-            if (__float_as_uint(d2) > *(volatile unsigned *)work) atomicMax(work, __float_as_uint(d2));
-            __threadfence();
-            if (atomicAdd(work + 1, 1u) == gridDim.x - 1u) s_last = 1u; // every other block's maximum is in
-        }
+    const float d2 = block_max_disp2<T>(pos, ref, N, b, s_max);
+    if (threadIdx.x == 0) {
+        if (__float_as_uint(d2) > *(volatile unsigned *)work) atomicMax(work, __float_as_uint(d2));
+        __threadfence();
+        if (atomicAdd(work + 1, 1u) == gridDim.x - 1u) s_last = 1u; // every other block's maximum is in
     }
     __syncthreads();
     if (s_last == 0u) return;
-    for (unsigned m = 0; m < mirror.n; ++m) {
-        const unsigned *src = (const unsigned *)mirror.src[m];
-        unsigned *dst = (unsigned *)mirror.dst[m];
-        for (unsigned w = threadIdx.x; w < mirror.words[m]; w += blockDim.x) dst[w] = __builtin_nontemporal_load(src + w);
+    if (CYCLE) {
+        for (unsigned m = 0; m < mirror.n; ++m) {
+            const unsigned *src = (const unsigned *)mirror.src[m];
+            unsigned *dst = (unsigned *)mirror.dst[m];
+            for (unsigned w = threadIdx.x; w < mirror.words[m]; w += blockDim.x) dst[w] = __builtin_nontemporal_load(src + w);
+        }
+        __threadfence_system();
+        __syncthreads();
     }
-    __threadfence_system();
-    __syncthreads();
     if (threadIdx.x == 0) {
-        // the cycle number is an unsigned WORD in the second slot (bit pattern, not a float value: as a float it stopped counting at
-        // 2^24 -- ten minutes of replayed cycles at 30 us per step).  The host compares modulo 2^32.
         const float worst = __uint_as_float(atomicExch(work, 0u));
-        const unsigned cycle = __float_as_uint(out[1]) + 1u;
         out[0] = worst;
-        out[1] = __uint_as_float(cycle);
         work[1] = 0u;
-        if (h_out != nullptr) {
-            h_out[0] = worst;
-            __threadfence_system();
-            *(volatile unsigned *)(h_out + 1) = cycle;
+        if (CYCLE) {
+            // the cycle number is an unsigned WORD in the second slot (bit pattern, not a float value: as a float it stopped counting
+            // at 2^24 -- ten minutes of replayed cycles at 30 us per step).  The host compares modulo 2^32.
+            const unsigned cycle = __float_as_uint(out[1]) + 1u;
+            out[1] = __uint_as_float(cycle);
+            if (h_out != nullptr) {
+                h_out[0] = worst;
+                __threadfence_system();
+                *(volatile unsigned *)(h_out + 1) = cycle;
+            }
         }
     }
 }
@@ -505,9 +504,9 @@ extern "C" int htfs_check_displacement2(const void *d_pos, const void *d_ref, in
     }
     unsigned grid = (N + 1023) / 1024;
     if (dtype == HTF_F32)
-        hipLaunchKernelGGL((check_disp_kernel<float>), dim3(grid), dim3(1024), 0, (hipStream_t)stream, (const float4 *)d_pos, (const float4 *)d_ref, N, make_sbox<float>(box), d_work, d_out, h_out, mr);
+        hipLaunchKernelGGL((check_disp_kernel<float, true>), dim3(grid), dim3(1024), 0, (hipStream_t)stream, (const float4 *)d_pos, (const float4 *)d_ref, N, make_sbox<float>(box), d_work, d_out, h_out, mr);
     else
-        hipLaunchKernelGGL((check_disp_kernel<double>), dim3(grid), dim3(1024), 0, (hipStream_t)stream, (const double4 *)d_pos, (const double4 *)d_ref, N, make_sbox<double>(box), d_work, d_out, h_out, mr);
+        hipLaunchKernelGGL((check_disp_kernel<double, true>), dim3(grid), dim3(1024), 0, (hipStream_t)stream, (const double4 *)d_pos, (const double4 *)d_ref, N, make_sbox<double>(box), d_work, d_out, h_out, mr);
     return check_launch("check_disp_kernel");
 }
 
@@ -528,26 +527,46 @@ __device__ __forceinline__ T reimage1(T x, double L, double c) {
     return L > 0.0 ? (T)((double)x - L * rint(((double)x - c) / L)) : x;
 }
 
+// The per-cell ordering is part of this kernel too (it was cell_order_kernel, a launch of its own between the scatter and this one):
+// the scatter's atomics fill a cell's span of `stage` in arbitrary order; the thread of slot s takes its particle k = stage[s],
+// finds the cell's span through cell_of[k] and RANKS k among the span's members (how many are smaller: indices are distinct), and
+// writes the sorted `order` entry and the tagged sorted position at span begin + rank.  Out of place: `stage` is only read here,
+// `order` and `dest` only written, every slot exactly once.  A span holds ~4 members on the fine grid; a cell of hundreds costs
+// its members a loop of hundreds each, no more.
+// `count` (nullable): the per-cell counts, left zero for the next binning by the first ncell threads of the range-table blocks (the
+// table has >= 1 row per cell).  It was cell_order_kernel's last act; it cannot move EARLIER than this launch -- cell_scan_kernel's
+// workgroups each sum the counts before their own chunk, so no block of the scan may zero what another still reads, and the
+// scatter's grid (one thread per position) need not cover the cells -- and here every reader of the counts (the scan) has
+// completed in stream order, while the next writer (the next binning's cell_index_count_kernel) has not begun.
 template <typename V>
 __global__ __launch_bounds__(256) void bins_finish_kernel(RangesArgs ra, unsigned nb_ranges, V *__restrict__ dest, const V *__restrict__ src,
-                                                          const int *__restrict__ order, unsigned n, int type_split, V *__restrict__ ref,
-                                                          unsigned n_ref, unsigned *__restrict__ counter, Reimage im, Gate gate) {
+                                                          const unsigned *__restrict__ stage, const unsigned *__restrict__ cell_of,
+                                                          unsigned *__restrict__ order, unsigned *__restrict__ count, unsigned n,
+                                                          int type_split, V *__restrict__ ref, unsigned n_ref,
+                                                          unsigned *__restrict__ counter, Reimage im, Gate gate) {
     if (gate.closed()) return;
     if (blockIdx.x < nb_ranges) {
-        cell_ranges_body(blockIdx.x * blockDim.x + threadIdx.x, ra);
+        const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+        if (count != nullptr && t < (unsigned)(ra.nx * ra.ny * ra.nz)) count[t] = 0u;
+        cell_ranges_body(t, ra);
         return;
     }
     const unsigned i = (blockIdx.x - nb_ranges) * blockDim.x + threadIdx.x;
     if (i == 0 && counter != nullptr) *counter += 1u;
     if (i >= n || i >= ra.cell_start[ra.nx * ra.ny * ra.nz]) return; // (arrays with inert rows: only the binned particles have an entry)
-    const unsigned k = (unsigned)order[i];
+    const unsigned k = stage[i];
     V p = src[k];
-    if (ref != nullptr && k < n_ref) ref[k] = p; // (order is a permutation: every reference position is written once)
+    const unsigned c = cell_of[k]; // (k is binned: never kDeadCell)
+    const unsigned cb = ra.cell_start[c], ce = ra.cell_start[c + 1];
+    unsigned slot = cb;
+    for (unsigned j = cb; j < ce; ++j) slot += stage[j] < k ? 1u : 0u;
+    order[slot] = k;
+    if (ref != nullptr && k < n_ref) ref[k] = p; // (stage is a permutation: every reference position is written once)
     p.x = reimage1(p.x, im.L[0], im.c[0]);
     p.y = reimage1(p.y, im.L[1], im.c[1]);
     p.z = reimage1(p.z, im.L[2], im.c[2]);
     set_tag(p.w, k | ((type_split >= 0 && scalar_as_int(p.w) >= type_split) ? kTagSide : 0u));
-    dest[i] = p;
+    dest[slot] = p;
 }
 
 // cell index of every particle and the cells' populations in one pass (htfs_cell_index + the first kernel of htfs_cell_sort)
@@ -610,7 +629,7 @@ __global__ __launch_bounds__(256) void cell_count_kernel(const unsigned *__restr
 // Round 4: one workgroup PER 2 048 cells instead of one for all of them (32 k cells at C3 took 45 us of dependent chunks, 5 us of
 // every MD step): workgroup b first sums the counts of the cells before its own (at most ncell reads per thread-block, from L2),
 // then scans its chunk.  The counts are no longer zeroed here -- another workgroup may still be summing them -- but by
-// cell_order_kernel, the last kernel of the sort.
+// the last kernel of the sort: cell_order_kernel (htfs_cell_sort), bins_finish_kernel (a rebuild).
 constexpr unsigned kScanThreads = 256, kScanPer = 8, kScanChunk = kScanThreads * kScanPer;
 __global__ __launch_bounds__(kScanThreads) void cell_scan_kernel(const unsigned *__restrict__ count, unsigned ncell,
                                                          unsigned *__restrict__ start, unsigned *__restrict__ cursor, Gate gate) {
@@ -670,7 +689,8 @@ __global__ __launch_bounds__(256) void cell_scatter_kernel(const unsigned *__res
     if (i < n && cell_of[i] != kDeadCell) order[atomicAdd(&cursor[cell_of[i]], 1u)] = i;
 }
 
-// the scatter's order inside a cell depends on the atomics' timing: sort each cell's few members
+// the scatter's order inside a cell depends on the atomics' timing: sort each cell's few members (the stepwise htfs_cell_sort
+// only: a rebuild ranks the members in bins_finish_kernel instead)
 __global__ __launch_bounds__(256) void cell_order_kernel(const unsigned *__restrict__ start, unsigned ncell,
                                                          unsigned *__restrict__ order, unsigned *__restrict__ count, Gate gate) {
     if (gate.closed()) return;
@@ -691,12 +711,21 @@ __global__ __launch_bounds__(256) void cell_order_kernel(const unsigned *__restr
 } // namespace htf
 
 // The first half of a binning scratch (the per-cell counts) must be zero on entry.  Every call that RUNS leaves it so
-// (cell_order_kernel) and a call the gate holds back does not touch it, so a caller that knows the last completed call on this
-// scratch used the same ncell may say so (htfs_nlist's scratch_clean) and save the memset; otherwise the words between the two
+// (cell_order_kernel; bins_finish_kernel in a rebuild) and a call the gate holds back does not touch it, so a caller that knows
+// the last completed call on this scratch used the same ncell may say so (htfs_nlist's scratch_clean) and save the memset; otherwise the words between the two
 // sizes are stale.  The stepwise htfs_cell_sort knows nothing of its caller and always zeroes.
 static int zero_counts(unsigned *count, unsigned ncell, hipStream_t s) {
     HTF_REQUIRE(((uintptr_t)count & 15) == 0, "binning scratch must be 16-byte aligned (cell_scan_kernel reads it with 16-byte loads)");
     HTF_CHECK_HIP(hipMemsetAsync(count, 0, (size_t)ncell * sizeof(unsigned), s));
+    return HTF_OK;
+}
+// ... and of an htfs_nlist's scratch, the two work words of the eager distance check beside the counts (zero before the first
+// check, left zero by every check: the same promise, the same flag)
+static int zero_nlist_scratch(const htfs_nlist *l, hipStream_t s) {
+    const unsigned ncell = (unsigned)(l->ncell3[0] * l->ncell3[1] * l->ncell3[2]);
+    HTF_REQUIRE(l->scratch && ncell > 0, "htfs_rebuild_nlist: no scratch, or no cells");
+    if (int rc = zero_counts(l->scratch, ncell, s)) return rc;
+    HTF_CHECK_HIP(hipMemsetAsync(l->scratch + HTFS_SCRATCH_WORK(ncell), 0, 2 * sizeof(unsigned), s));
     return HTF_OK;
 }
 
@@ -858,6 +887,8 @@ extern "C" int htfs_cell_index(const void *d_pos, int dtype, unsigned Ntot, cons
 struct FinishArgs {
     unsigned n;
     htf::Reimage im;
+    const unsigned *stage; // the scatter's unordered members per cell (htfs_nlist's scratch)
+    unsigned *count;       // the per-cell counts, zeroed for the next binning
 };
 
 static int build_nlist_impl(const htfs_nlist *l, const void *d_pos, int dtype, unsigned N, htf_stream stream, htf::Gate gate,
@@ -897,10 +928,10 @@ static int build_nlist_impl(const htfs_nlist *l, const void *d_pos, int dtype, u
         const unsigned nb = nb_ranges + (fin->n + 255) / 256 + (fin->n == 0 ? 1u : 0u);
         if (dtype == HTF_F32)
             hipLaunchKernelGGL((bins_finish_kernel<float4>), dim3(nb), dim3(256), 0, (hipStream_t)stream, ra, nb_ranges, (float4 *)l->pos_sorted,
-                               (const float4 *)d_pos, (const int *)l->order, fin->n, type_split, (float4 *)l->ref, N, l->counter, fin->im, gate);
+                               (const float4 *)d_pos, fin->stage, l->cell_of, l->order, fin->count, fin->n, type_split, (float4 *)l->ref, N, l->counter, fin->im, gate);
         else
             hipLaunchKernelGGL((bins_finish_kernel<double4>), dim3(nb), dim3(256), 0, (hipStream_t)stream, ra, nb_ranges, (double4 *)l->pos_sorted,
-                               (const double4 *)d_pos, (const int *)l->order, fin->n, type_split, (double4 *)l->ref, N, l->counter, fin->im, gate);
+                               (const double4 *)d_pos, fin->stage, l->cell_of, l->order, fin->count, fin->n, type_split, (double4 *)l->ref, N, l->counter, fin->im, gate);
     }
     const bool fine = stencil3[0] == 2 || stencil3[1] == 2 || stencil3[2] == 2; // short ranges: 8-lane groups waste fewer lanes
 #define HTFS_NL(T, V4, G)                                                                                              \
@@ -951,8 +982,9 @@ extern "C" int htfs_build_nlist(const htfs_nlist *nl, const void *d_pos, int dty
 }
 
 // The whole rebuild -- htfs_cell_index, htfs_cell_sort, htfs_gather4_tagged, htfs_build_nlist and the commit of the reference
-// positions -- in six launches instead of nine (index + count in one kernel; range table, sorted copy and commit in one): the
-// small kernels are launch- and latency-bound, and a gated rebuild pays for every one of them even when the gate is closed.
+// positions -- in FIVE launches instead of nine (index + count in one kernel; the order inside a cell, range table, sorted copy,
+// commit and the zeroing of the counts in one): the small kernels are launch- and latency-bound, and a gated rebuild pays for every
+// one of them even when the gate is closed.
 // Candidates may include ghosts behind the N local rows (and inert rows anywhere: a decomposed system's fixed-capacity arrays):
 // Ntot positions binned, N rows searched and committed.
 static int rebuild_nlist_impl(const htfs_nlist *l, const void *d_pos, int dtype, unsigned N, unsigned Ntot, bool scratch_clean,
@@ -966,9 +998,9 @@ static int rebuild_nlist_impl(const htfs_nlist *l, const void *d_pos, int dtype,
     const unsigned ncell = (unsigned)(ncell3[0] * ncell3[1] * ncell3[2]);
     HTF_REQUIRE(ncell > 0, "htfs_rebuild_nlist: no cells");
     hipStream_t s = (hipStream_t)stream;
-    unsigned *count = l->scratch, *cursor = l->scratch + ncell;
+    unsigned *count = l->scratch, *cursor = l->scratch + ncell, *stage = l->scratch + HTFS_SCRATCH_STAGE(ncell);
     if (!scratch_clean)
-        if (int rc = zero_counts(count, ncell, s)) return rc;
+        if (int rc = zero_nlist_scratch(l, s)) return rc;
     const unsigned grid = (Ntot + 255) / 256;
     Reimage im = {};
     for (int d = 0; d < 3; ++d) {
@@ -983,9 +1015,9 @@ static int rebuild_nlist_impl(const htfs_nlist *l, const void *d_pos, int dtype,
         hipLaunchKernelGGL((cell_index_count_kernel<double>), dim3(grid), dim3(256), 0, s, (const double4 *)d_pos, Ntot, make_sbox<double>(box),
                            ncell3[0], ncell3[1], ncell3[2], l->cell_of, count, im, gate);
     hipLaunchKernelGGL(cell_scan_kernel, dim3((ncell + kScanChunk - 1) / kScanChunk), dim3(kScanThreads), 0, s, count, ncell, l->cell_start, cursor, gate);
-    hipLaunchKernelGGL(cell_scatter_kernel, dim3(grid), dim3(256), 0, s, l->cell_of, Ntot, cursor, l->order, gate);
-    hipLaunchKernelGGL(cell_order_kernel, dim3((ncell + 255) / 256), dim3(256), 0, s, l->cell_start, ncell, l->order, count, gate);
-    const FinishArgs fin = {Ntot, im};
+    // (into the staging words, not into `order`: bins_finish_kernel orders each cell's members out of place)
+    hipLaunchKernelGGL(cell_scatter_kernel, dim3(grid), dim3(256), 0, s, l->cell_of, Ntot, cursor, stage, gate);
+    const FinishArgs fin = {Ntot, im, stage, count};
     return build_nlist_impl(l, d_pos, dtype, N, stream, gate, &fin);
 }
 
@@ -994,22 +1026,38 @@ extern "C" int htfs_rebuild_nlist(const htfs_nlist *nl, const void *d_pos, int d
     return rebuild_nlist_impl(nl, d_pos, dtype, N, Ntot, scratch_clean != 0, stream, htf::kOpenGate);
 }
 
-// A whole check step of a device-decided list in ONE call (the host's share of a small system's step is its enqueue): the
-// displacement word zeroed and filled, the rebuild behind a gate on it, and the two status words copied to pinned host memory
-// for the NEXT check to read (nullable).
+// A whole check step of a device-decided list in ONE call (the host's share of a small system's step is its enqueue), SEVEN stream
+// operations, five of them gated: the displacement word filled by ONE launch (check_disp_kernel<T, false>: the blocks accumulate
+// into the scratch's two work words, the last one -- by ticket -- publishes *d_disp2 and leaves the work words zero, where a memset
+// and max_disp_kernel were two), the five launches of the rebuild behind a gate on that word, and the two status words copied to
+// pinned host memory for the NEXT check to read (nullable).  The copy stays a stream operation of its own: the words are written by
+// the search, the LAST kernel of the check, and the host polls them before it enqueues the next check -- the check kernel's
+// mailman (htfs_check_displacement2) would deliver them one check later than CellNlist's callers are promised.
 extern "C" int htfs_check_rebuild_nlist(const htfs_nlist *nl, const void *d_pos, int dtype, unsigned N, unsigned Ntot, int scratch_clean,
                                         float *d_disp2, double threshold2, unsigned *d_stat2, unsigned *h_stat2, htf_stream stream) {
-    HTF_REQUIRE(nl && nl->ref && d_disp2 && d_stat2, "htfs_check_rebuild_nlist: null pointer");
+    using namespace htf;
+    HTF_REQUIRE(nl && nl->ref && nl->scratch && d_pos && d_disp2 && d_stat2, "htfs_check_rebuild_nlist: null pointer");
     if (N == 0) return HTF_OK;
-    HTF_CHECK_HIP(hipMemsetAsync(d_disp2, 0, sizeof(float), (hipStream_t)stream));
-    int rc = htfs_max_displacement2(d_pos, nl->ref, dtype, N, &nl->box, d_disp2, stream);
+    const unsigned ncell = (unsigned)(nl->ncell3[0] * nl->ncell3[1] * nl->ncell3[2]);
+    HTF_REQUIRE(ncell > 0, "htfs_check_rebuild_nlist: no cells");
+    hipStream_t s = (hipStream_t)stream;
+    unsigned *work = nl->scratch + HTFS_SCRATCH_WORK(ncell);
+    if (!scratch_clean) // (before the check kernel, whose work words are part of it: the rebuild below then finds it clean)
+        if (int rc = zero_nlist_scratch(nl, s)) return rc;
+    const unsigned grid = (N + 1023) / 1024;
+    const htfs_mirror none = {};
+    if (dtype == HTF_F32)
+        hipLaunchKernelGGL((check_disp_kernel<float, false>), dim3(grid), dim3(1024), 0, s, (const float4 *)d_pos, (const float4 *)nl->ref, N, make_sbox<float>(&nl->box), work, d_disp2, (float *)nullptr, none);
+    else
+        hipLaunchKernelGGL((check_disp_kernel<double, false>), dim3(grid), dim3(1024), 0, s, (const double4 *)d_pos, (const double4 *)nl->ref, N, make_sbox<double>(&nl->box), work, d_disp2, (float *)nullptr, none);
+    int rc = check_launch("check_disp_kernel");
     if (rc != HTF_OK) return rc;
     htfs_nlist l = *nl;
     l.max_neigh = d_stat2;
     l.counter = d_stat2 + 1;
-    rc = rebuild_nlist_impl(&l, d_pos, dtype, N, Ntot, scratch_clean != 0, stream, htf::Gate{d_disp2, (float)threshold2});
+    rc = rebuild_nlist_impl(&l, d_pos, dtype, N, Ntot, true, stream, Gate{d_disp2, (float)threshold2});
     if (rc != HTF_OK) return rc;
     if (h_stat2 != nullptr)
-        HTF_CHECK_HIP(hipMemcpyAsync(h_stat2, d_stat2, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream));
+        HTF_CHECK_HIP(hipMemcpyAsync(h_stat2, d_stat2, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, s));
     return HTF_OK;
 }

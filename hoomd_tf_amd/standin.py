@@ -258,7 +258,8 @@ class CellNlist:
             self._cell_of = torch.empty(Ntot, dtype=torch.int32, device=s.device)
             self._order = torch.empty(Ntot, dtype=torch.int32, device=s.device)
             self._cell_start = torch.empty(ncell + 1, dtype=torch.int32, device=s.device)
-            self._bin_scratch = torch.empty(2 * ncell, dtype=torch.int32, device=s.device)
+            # htf_standin.h HTFS_SCRATCH_WORDS: counts, cursors, the check's two work words (zero before their first use), staging
+            self._bin_scratch = torch.zeros(2 * ncell + 2 + Ntot, dtype=torch.int32, device=s.device)
             self._pos_sorted = torch.empty((Ntot, 4), dtype=s.pos.dtype, device=s.device)
             # candidate ranges per (cell, stencil row): this list's own table (htf_standin.h HTFS_RANGE_WORDS), part of what a
             # captured step carries by address
@@ -286,7 +287,7 @@ class CellNlist:
 
     def _rebuild_fixed(self, Ntot):
         """Every rebuild after the first of a fixed-capacity system: nothing to size, nothing to read back -- binning, sorted
-        copy, range table, search and commit in six launches (htfs_rebuild_nlist) where the separate calls take ten."""
+        copy, range table, search and commit in five launches (htfs_rebuild_nlist) where the separate calls take ten."""
         self._poll_max()   # the PREVIOUS build's largest row (pinned copy behind it): no wait
         self._enqueue_rebuild(Ntot, gated=False)
         self._copy_max_late()
@@ -357,7 +358,7 @@ class CellNlist:
         """The one route to a rebuild after the first: ONE C call on the descriptor.  ``gated``: behind the distance check,
         decided on the device, status words to pinned memory (htf_standin.h htfs_check_rebuild_nlist); else unconditional."""
         s, d = self.sys, self._desc
-        # the binning scratch is this object's own and every completed binning leaves its counts zero (cell_order_kernel): no memset
+        # the binning scratch is this object's own and every completed binning leaves its counts zero (its last small kernel): no memset
         key = (d.scratch, self._grid[2])
         clean = int(self._scratch_clean == key)
         self._scratch_clean = None   # (a call that fails half way leaves the counts dirty: the next one zeroes them again)

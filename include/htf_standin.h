@@ -44,6 +44,11 @@ HTF_API int htfs_check_displacement2(const void *d_pos, const void *d_ref, int d
  *   nlist[i*pitch + c] = k  for every k != i with |minimage(r_k - r_i)| <= r_list,
  *   n_neigh[i] = count, head_list[i] = i*pitch. */
 #define HTFS_RANGE_WORDS(ncell, stencil_y, stencil_z) (4u * (size_t)(ncell) * (2u * (stencil_y) + 1u) * (2u * (stencil_z) + 1u))
+/* htfs_nlist's scratch, in 32-bit words: counts | cursors | work words | staging (2 * ncell + 2 + Ntot; until the per-cell ordering
+ * moved into the rebuild's finishing kernel it was 2 * ncell) */
+#define HTFS_SCRATCH_WORK(ncell) (2u * (size_t)(ncell))
+#define HTFS_SCRATCH_STAGE(ncell) (HTFS_SCRATCH_WORK(ncell) + 2u)
+#define HTFS_SCRATCH_WORDS(ncell, Ntot) (HTFS_SCRATCH_STAGE(ncell) + (size_t)(Ntot))
 typedef struct htfs_nlist {
     htf_box box;            /* the box the list is binned and searched on (a brick + its ghost layer under a local grid) */
     double r_list;
@@ -55,10 +60,14 @@ typedef struct htfs_nlist {
     /* scratch of a rebuild, Ntot = local rows + ghosts */
     unsigned *cell_of;      /* [Ntot] cell index of every particle; 0xFFFFFFFF for an INERT row (x = NaN: fixed-capacity arrays of
                              * a decomposed system, hoomd_tf_amd/brick.py -- such rows are in no cell) */
-    unsigned *scratch;      /* [2 * ncell], 16-byte aligned (checked).  Its first half (the per-cell counts) is zero after every
-                             * COMPLETED binning on it with the same ncell, as long as nothing else has written the buffer: that is
-                             * what a caller passing scratch_clean != 0 promises, and the call then skips its memset (two dependent
-                             * nodes of a captured rebuild; a rebuild a closed gate holds back does not touch the counts either) */
+    unsigned *scratch;      /* [HTFS_SCRATCH_WORDS(ncell, Ntot)], 16-byte aligned (checked): the per-cell counts [ncell], the scatter's
+                             * cursors [ncell], the two work words of htfs_check_rebuild_nlist's distance check, and [Ntot] staging
+                             * words (every cell's members in the order the scatter's atomics left them, before the rebuild ranks
+                             * them into `order`).  The counts and the work words are zero after every COMPLETED call on it with the
+                             * same ncell, as long as nothing else has written the buffer: that is what a caller passing
+                             * scratch_clean != 0 promises, and the call then skips its memsets (dependent nodes of a captured
+                             * rebuild; a rebuild a closed gate holds back does not touch the counts either).  htfs_cell_sort uses
+                             * the first 2 * ncell words of the same buffer and keeps the promise */
     unsigned *cell_start;   /* [ncell + 1] first slot of cell c; the last word is the binned total */
     unsigned *order;        /* [Ntot] particle indices sorted by cell, ascending index inside a cell (deterministic) */
     void *pos_sorted;       /* [Ntot] Scalar4 pos[order] with  order[i] | (type >= type_split) << 31  in w (Ntot <= 2^31): a cell's
@@ -96,16 +105,18 @@ HTF_API int htfs_gather4_tagged_live(void *d_dest, const void *d_src, const int 
 /* range table + search of the N local rows of d_pos, on cell_start and pos_sorted as the calls above left them */
 HTF_API int htfs_build_nlist(const htfs_nlist *nl, const void *d_pos, int dtype, unsigned N, htf_stream stream);
 
-/* The whole rebuild in one call and six launches (the stepwise calls take ten): Ntot >= N positions binned, the N local rows
+/* The whole rebuild in one call and five launches (the stepwise calls take ten): Ntot >= N positions binned, the N local rows
  * searched, ref and counter committed. */
 HTF_API int htfs_rebuild_nlist(const htfs_nlist *nl, const void *d_pos, int dtype, unsigned N, unsigned Ntot, int scratch_clean,
                                htf_stream stream);
 
-/* One check step of a device-decided list in one call, WITHOUT a host decision: *d_disp2 <- 0, htfs_max_displacement2 (from
- * nl->ref, required) into it, then the rebuild above with every kernel returning at entry unless *d_disp2 > threshold2 when it
+/* One check step of a device-decided list in one call, WITHOUT a host decision: *d_disp2 <- max_i |minimage(pos_i - ref_i)|^2
+ * (from nl->ref, required; the value htfs_max_displacement2 gives, by one launch that accumulates in the scratch's work words
+ * and needs no zeroing), then the rebuild above with every kernel returning at entry unless *d_disp2 > threshold2 when it
  * RUNS; the caller enqueues it behind every distance check and never reads the result back.  d_stat2 stands in for
  * nl->max_neigh and nl->counter (d_stat2[0] = largest row, d_stat2[1] = rebuilds); h_stat2 (nullable; pinned host memory)
- * receives an asynchronous copy of the two words for a later check to read. */
+ * receives an asynchronous copy of the two words, behind the search, for a later check to read.  Seven stream operations,
+ * five of them gated. */
 HTF_API int htfs_check_rebuild_nlist(const htfs_nlist *nl, const void *d_pos, int dtype, unsigned N, unsigned Ntot, int scratch_clean,
                                      float *d_disp2, double threshold2, unsigned *d_stat2, unsigned *h_stat2, htf_stream stream);
 

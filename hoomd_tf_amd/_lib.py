@@ -264,26 +264,17 @@ NLIST_PROTOTYPES = {
     "htf_nlist_cells_forward": (_i, [_vp, _u, _u, _vp, C.c_float, _u, _u, _u, _u, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
-# the descriptor network (include/htf_desc.h; hoomd_tf_amd/layers.py DescriptorMLP)
-DESC_PROTOTYPES = {
-    "htf_desc_forces": (_i, [_vp, _i, _u, _u, _u, _u, _u, _u, _i, _vp, _vp, C.c_float, _vp, _i, _vp, _vp]),
-    "htf_desc_descriptor": (_i, [_vp, _i, _u, _u, _u, _u, _vp, C.c_float, _vp, _i, _vp]),
-}
-
-# force matching for the descriptor network (include/htf_desc_train.h; DescriptorMLP.loss_gradient)
-DESC_TRAIN_PROTOTYPES = {
-    "htf_dtrain_scratch_floats": (_sz, [_u, _u, _u, _u, _u]),
-    "htf_dtrain_loss_grad": (_i, [_vp, _i, _u, _u, _u, _u, _u, _u, _i, _vp, _vp, C.c_float, _vp, _i, _vp, _vp, _vp, _vp]),
-}
-
-# the descriptor network with a cutoff and over a row list (include/htf_bp.h; DescriptorMLP(r_cut=..., n_species=...)): the two
-# tables above with (rows, n_rows, r_cut) before the stream, the descriptor entry with r_cut alone
+# the descriptor network (include/htf_bp.h; hoomd_tf_amd/layers.py DescriptorMLP): forces, descriptor, force-matching sweep
 BP_PROTOTYPES = {
     "htf_bp_forces": (_i, [_vp, _i, _u, _u, _u, _u, _u, _u, _i, _vp, _vp, C.c_float, _vp, _i, _vp, _vp, _u, C.c_float, _vp]),
     "htf_bp_descriptor": (_i, [_vp, _i, _u, _u, _u, _u, _vp, C.c_float, _vp, _i, C.c_float, _vp]),
     "htf_bp_scratch_floats": (_sz, [_u, _u, _u, _u, _u]),
     "htf_bp_loss_grad": (_i, [_vp, _i, _u, _u, _u, _u, _u, _u, _i, _vp, _vp, C.c_float, _vp, _i, _vp, _vp, _vp, _vp, _u, C.c_float, _vp]),
 }
+
+# every table above: what the ctypes and the pybind11 binding both declare
+ALL_PROTOTYPES = tuple((name, proto) for table in (PROTOTYPES, STANDIN_PROTOTYPES, CG_PROTOTYPES, GEOM_PROTOTYPES, NLIST_PROTOTYPES,
+                                                   BP_PROTOTYPES) for name, proto in table.items())
 
 
 ABI_VERSION = 5  # include/htf_amd.h HTF_AMD_ABI_VERSION: the struct layouts the ctypes Structures of this file mirror
@@ -295,10 +286,7 @@ def _load():
             "hoomd_tf_amd: %s is missing. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C hoomd_tf_amd/csrc`. There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in (list(PROTOTYPES.items()) + list(STANDIN_PROTOTYPES.items()) + list(CG_PROTOTYPES.items())
-                              + list(GEOM_PROTOTYPES.items()) + list(NLIST_PROTOTYPES.items())
-                              + list(DESC_PROTOTYPES.items()) + list(DESC_TRAIN_PROTOTYPES.items())
-                              + list(BP_PROTOTYPES.items())):
+    for name, (res, args) in ALL_PROTOTYPES:
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -342,10 +330,7 @@ class _PybindLib:
 
     def __init__(self, mod):
         self._mod = mod
-        for name, (res, args) in (list(PROTOTYPES.items()) + list(STANDIN_PROTOTYPES.items()) + list(CG_PROTOTYPES.items())
-                                  + list(GEOM_PROTOTYPES.items()) + list(NLIST_PROTOTYPES.items())
-                                  + list(DESC_PROTOTYPES.items()) + list(DESC_TRAIN_PROTOTYPES.items())
-                                  + list(BP_PROTOTYPES.items())):
+        for name, (res, args) in ALL_PROTOTYPES:
             fn = getattr(mod, name)  # AttributeError if the module lacks a declared symbol
             ptr_at = tuple(i for i, t in enumerate(args) if _is_pointer(t))
             setattr(self, name, self._wrap(fn, ptr_at, res is _vp))

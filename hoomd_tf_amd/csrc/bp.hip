@@ -1,11 +1,13 @@
-// The descriptor network with a smooth cutoff and over a row list (include/htf_bp.h, htf.DescriptorMLP(r_cut=..., n_species=...)).
+// The descriptor network (include/htf_bp.h, htf.DescriptorMLP): per particle, D = n_types * K Gaussian channel sums of the
+// neighbor distances -> Dense(H1) -> Dense(H2) -> Dense(1) = E_i, forces F_i = 2 sum_j dE_i/dx_ij (compute_nlist_forces), and
+// the force-matching sweep over the same rows.  The layer's one translation unit.
 //
-// The row bodies are desc_row.h's and dtrain_row.h's, instantiated here with the row list on and the cutoff on or off, so a
-// row evaluated here without a cutoff carries the bits desc_mlp.hip and desc_train.hip give it.  One network per species is
-// one launch per species: Python partitions the batch into ascending row lists and passes each with its species' weights.
-// Every output row is written by the one launch that lists it: no memset, no atomics.  The sweep's partials are a function
-// of n_rows alone and desc_train.hip's reduction adds them, so entry q of the list is row q of a batch of n_rows, bit for bit.
-// Built with -ffp-contract=on like desc_mlp.o and desc_train.o (csrc/Makefile).
+// The rows themselves are desc_row.h's (forces, descriptor) and dtrain_row.h's (sweep), instantiated here with the cutoff on
+// or off and with or without a row list (selected by d_rows alone).  One network per species is one launch per species:
+// Python partitions the batch into ascending row lists and passes each with its species' weights.  Every output row is
+// written by the one launch that lists it: no memset, no atomics.  The sweep's partials are a function of n_rows alone and
+// the reduction below adds them in a fixed order, so entry q of the list is row q of a batch of n_rows, bit for bit.
+// Built with -ffp-contract=on (csrc/Makefile).
 #include "htf_bp.h"
 #include "desc_row.h"
 #include "dtrain_row.h"
@@ -13,21 +15,45 @@
 namespace htf {
 namespace {
 
-template <bool FORCES, bool TANH, bool VIRIAL, bool CUT, typename IT>
+template <bool FORCES, bool TANH, bool VIRIAL, bool CUT, bool LIST, typename IT>
 __global__ __launch_bounds__(256) void bp_rows_kernel(const typename Vec4<IT>::type *__restrict__ nlist, const int *__restrict__ rows,
                                                       unsigned n, unsigned NN, const float *__restrict__ weights,
                                                       const float *__restrict__ mu, int K, int T, int H1, int H2, float gap, float rc,
                                                       void *__restrict__ out, int out_f64, void *__restrict__ virial9) {
-    desc_rows<FORCES, TANH, VIRIAL, CUT, true, IT>(nlist, rows, n, NN, weights, mu, K, T, H1, H2, gap, rc, out, out_f64, virial9);
+    desc_rows<FORCES, TANH, VIRIAL, CUT, LIST, IT>(nlist, rows, n, NN, weights, mu, K, T, H1, H2, gap, rc, out, out_f64, virial9);
 }
 
-template <bool TANH, bool CUT, typename IT>
+template <bool TANH, bool CUT, bool LIST, typename IT>
 __global__ __launch_bounds__(256, 1) void bp_sweep_kernel(const typename Vec4<IT>::type *__restrict__ nlist, const int *__restrict__ rows,
                                                           unsigned n, unsigned NN, const float *__restrict__ weights,
                                                           const float *__restrict__ mu, int K, int T, int H1, int H2, float gap, float rc,
                                                           const void *__restrict__ labels, int labels_f64,
                                                           const float4 *__restrict__ pred, float *__restrict__ partials) {
-    dtrain_rows<TANH, CUT, true, IT>(nlist, rows, n, NN, weights, mu, K, T, H1, H2, gap, rc, labels, labels_f64, pred, partials);
+    dtrain_rows<TANH, CUT, LIST, IT>(nlist, rows, n, NN, weights, mu, K, T, H1, H2, gap, rc, labels, labels_f64, pred, partials);
+}
+
+// accum[p] = sum over the blocks' partials, in a fixed order: wave w of a block adds partials w, w + 4, ... for 64 entries,
+// then the four sums are added as (0 + 1) + (2 + 3).  The gradient entries carry the factor 2 of d SSR = 2 sum dQ.
+__global__ __launch_bounds__(256) void dtrain_reduce_kernel(const float *__restrict__ partials, unsigned nparts, unsigned n,
+                                                            float *__restrict__ accum) {
+    __shared__ float s[4][64];
+    const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const unsigned p = blockIdx.x * 64u + lane;
+    float v = 0.f;
+    if (p < n)
+        for (unsigned g = wave; g < nparts; g += 4) v += partials[(size_t)g * n + p];
+    s[wave][lane] = v;
+    __syncthreads();
+    if (wave == 0 && p < n) {
+        const float t = (s[0][lane] + s[1][lane]) + (s[2][lane] + s[3][lane]);
+        accum[p] = p == 0 ? t : 2.0f * t;
+    }
+}
+
+// nparts may be 0: accum is then zero-filled
+int dtrain_reduce_launch(const float *d_partials, unsigned nparts, unsigned n, float *d_accum, hipStream_t stream) {
+    hipLaunchKernelGGL(dtrain_reduce_kernel, dim3((n + 63u) / 64u), dim3(256), 0, stream, d_partials, nparts, n, d_accum);
+    return check_launch("dtrain_reduce_kernel");
 }
 
 int bp_check(unsigned B, unsigned n_rows, float r_cut) {
@@ -52,17 +78,21 @@ extern "C" int htf_bp_forces(const void *d_nlist, int nlist_dtype, unsigned B, u
     const size_t lds = desc_lds_forces(K, n_types, H1, H2);
     const int out_f64 = force_dtype == HTF_F64;
     const hipStream_t s = (hipStream_t)stream;
-#define HTF_BK(TANH, VIR, CUT, T, V4)                                                                                             \
-    hipLaunchKernelGGL((bp_rows_kernel<true, TANH, VIR, CUT, T>), dim3(desc_grid(n_rows)), dim3(256), lds, s, (const V4 *)d_nlist, \
-                       d_rows, n_rows, NN, d_weights, d_mu, (int)K, (int)n_types, (int)H1, (int)H2, gap, r_cut, d_force, out_f64, \
+#define HTF_BK(TANH, VIR, CUT, LIST, T, V4)                                                                                            \
+    hipLaunchKernelGGL((bp_rows_kernel<true, TANH, VIR, CUT, LIST, T>), dim3(desc_grid(n_rows)), dim3(256), lds, s, (const V4 *)d_nlist, \
+                       d_rows, n_rows, NN, d_weights, d_mu, (int)K, (int)n_types, (int)H1, (int)H2, gap, r_cut, d_force, out_f64,        \
                        d_virial9)
-#define HTF_BK2(TANH, VIR, CUT)                                                                                                   \
-    do {                                                                                                                          \
-        if (nlist_dtype == HTF_F32) HTF_BK(TANH, VIR, CUT, float, float4); else HTF_BK(TANH, VIR, CUT, double, double4);          \
+#define HTF_BK1(TANH, VIR, CUT, LIST)                                                                                                  \
+    do {                                                                                                                               \
+        if (nlist_dtype == HTF_F32) HTF_BK(TANH, VIR, CUT, LIST, float, float4); else HTF_BK(TANH, VIR, CUT, LIST, double, double4);   \
     } while (0)
-#define HTF_BK3(TANH, VIR)                                                                                                        \
-    do {                                                                                                                          \
-        if (r_cut > 0.0f) HTF_BK2(TANH, VIR, true); else HTF_BK2(TANH, VIR, false);                                               \
+#define HTF_BK2(TANH, VIR, CUT)                                                                                                        \
+    do {                                                                                                                               \
+        if (d_rows) HTF_BK1(TANH, VIR, CUT, true); else HTF_BK1(TANH, VIR, CUT, false);                                                \
+    } while (0)
+#define HTF_BK3(TANH, VIR)                                                                                                             \
+    do {                                                                                                                               \
+        if (r_cut > 0.0f) HTF_BK2(TANH, VIR, true); else HTF_BK2(TANH, VIR, false);                                                    \
     } while (0)
     if (activation == HTF_ACT_TANH) {
         if (d_virial9) HTF_BK3(true, true); else HTF_BK3(true, false);
@@ -71,6 +101,7 @@ extern "C" int htf_bp_forces(const void *d_nlist, int nlist_dtype, unsigned B, u
     }
 #undef HTF_BK3
 #undef HTF_BK2
+#undef HTF_BK1
 #undef HTF_BK
     return check_launch("bp_rows_kernel");
 }
@@ -86,7 +117,7 @@ extern "C" int htf_bp_descriptor(const void *d_nlist, int nlist_dtype, unsigned 
     const int out_f64 = out_dtype == HTF_F64;
     const hipStream_t s = (hipStream_t)stream;
 #define HTF_BG(CUT, T, V4)                                                                                                        \
-    hipLaunchKernelGGL((bp_rows_kernel<false, false, false, CUT, T>), dim3(desc_grid(B)), dim3(256), lds, s, (const V4 *)d_nlist,  \
+    hipLaunchKernelGGL((bp_rows_kernel<false, false, false, CUT, false, T>), dim3(desc_grid(B)), dim3(256), lds, s, (const V4 *)d_nlist,  \
                        (const int *)nullptr, B, NN, (const float *)nullptr, d_mu, (int)K, (int)n_types, 0, 0, gap, r_cut, d_out,   \
                        out_f64, nullptr)
     if (r_cut > 0.0f) {
@@ -120,13 +151,17 @@ extern "C" int htf_bp_loss_grad(const void *d_nlist, int nlist_dtype, unsigned B
     if (grid) {
         const size_t lds = dtrain_lds(K, n_types, H1, H2);
         const int l64 = labels_dtype == HTF_F64;
-#define HTF_BT(TANH, CUT, T, V4)                                                                                                  \
-    hipLaunchKernelGGL((bp_sweep_kernel<TANH, CUT, T>), dim3(grid), dim3(256), lds, s, (const V4 *)d_nlist, d_rows, n_rows, NN,    \
-                       d_weights, d_mu, (int)K, (int)n_types, (int)H1, (int)H2, gap, r_cut, d_labels, l64, (const float4 *)d_pred, \
+#define HTF_BT(TANH, CUT, LIST, T, V4)                                                                                                 \
+    hipLaunchKernelGGL((bp_sweep_kernel<TANH, CUT, LIST, T>), dim3(grid), dim3(256), lds, s, (const V4 *)d_nlist, d_rows, n_rows, NN,   \
+                       d_weights, d_mu, (int)K, (int)n_types, (int)H1, (int)H2, gap, r_cut, d_labels, l64, (const float4 *)d_pred,      \
                        d_scratch)
-#define HTF_BT2(TANH, CUT)                                                                                                        \
-    do {                                                                                                                          \
-        if (nlist_dtype == HTF_F32) HTF_BT(TANH, CUT, float, float4); else HTF_BT(TANH, CUT, double, double4);                    \
+#define HTF_BT1(TANH, CUT, LIST)                                                                                                       \
+    do {                                                                                                                               \
+        if (nlist_dtype == HTF_F32) HTF_BT(TANH, CUT, LIST, float, float4); else HTF_BT(TANH, CUT, LIST, double, double4);             \
+    } while (0)
+#define HTF_BT2(TANH, CUT)                                                                                                             \
+    do {                                                                                                                               \
+        if (d_rows) HTF_BT1(TANH, CUT, true); else HTF_BT1(TANH, CUT, false);                                                          \
     } while (0)
         if (activation == HTF_ACT_TANH) {
             if (r_cut > 0.0f) HTF_BT2(true, true); else HTF_BT2(true, false);
@@ -134,6 +169,7 @@ extern "C" int htf_bp_loss_grad(const void *d_nlist, int nlist_dtype, unsigned B
             if (r_cut > 0.0f) HTF_BT2(false, true); else HTF_BT2(false, false);
         }
 #undef HTF_BT2
+#undef HTF_BT1
 #undef HTF_BT
         const int rl = check_launch("bp_sweep_kernel");
         if (rl != HTF_OK) return rl;

@@ -1,4 +1,4 @@
-// The descriptor network's rows, written once for desc_mlp.hip (include/htf_desc.h) and bp.hip (include/htf_bp.h).
+// The descriptor network's rows (bp.hip, include/htf_bp.h): forces, energy and virial, or the descriptor alone.
 //
 // One wave64 per particle row, the shape of topk_mlp.hip.  Each lane holds up to four slots of the row (NN <= 256) in
 // registers: pair vector, distance and type, read once (16 B per slot, 32 B from an fp64 tensor).  Channel k of type t is
@@ -17,13 +17,13 @@
 // descriptor-only entry runs the same code for G.  Built with -ffp-contract=on (csrc/Makefile): multiply-adds are fused
 // only inside a source expression, so both instantiations (descriptor only, forces) form G identically.
 //
-// Two compile-time switches serve bp.hip and are compiled out for desc_mlp.hip's kernel:
+// Two compile-time switches beside the outputs:
 //   CUT   the cosine cutoff fc(r) = 0.5 (cos(pi r / rc) + 1), r < rc, multiplied into every Gaussian.  A slot at r >= rc is
 //         dropped where the slots are read, exactly like a padded one; fc and fc' = -0.5 (pi / rc) sin(pi r / rc) are formed
 //         once per slot where its distance is (sincospif: the reduction of r / rc in [0, 1) is exact) and kept, two
 //         registers per slot.  dE/dr = fc c_der sum_k g_k d_k e_k + fc' sum_k g_k e_k: a second accumulator per slot.
-//   LIST  wave work item q handles row rows[q] (rows may still be null: row q).  Outputs are indexed by the row.
-// With both off the code is the kernel desc_mlp.hip has always had, expression for expression.
+//   LIST  wave work item q handles row rows[q] instead of row q; the launcher selects it by whether it was given a list.
+//         Outputs are indexed by the row.  Without it the row index costs the default route nothing.
 #ifndef HTF_DESC_ROW_H_
 #define HTF_DESC_ROW_H_
 #include "htf_common.h"
@@ -57,7 +57,7 @@ __device__ __forceinline__ void line_publish(float *line, unsigned lane, float v
 __host__ __device__ inline int desc_lds_weights(int D, int H1, int H2) { return D * (H1 + 1) + H1 + H1 * (H2 + 1) + H2 + H2 + 1; }
 
 // FORCES = false: G alone, written to out [B][D].  FORCES = true: out [B][4] (f, E) and, with VIRIAL, virial9 [B][9].
-// n work items: rows 0 .. n - 1, or rows[0 .. n - 1] with LIST and a non-null list.
+// n work items: rows 0 .. n - 1, or rows[0 .. n - 1] with LIST (rows is then not null).
 template <bool FORCES, bool TANH, bool VIRIAL, bool CUT, bool LIST, typename IT>
 __device__ __forceinline__ void desc_rows(const typename Vec4<IT>::type *__restrict__ nlist, const int *__restrict__ rows, unsigned n,
                                           unsigned NN, const float *__restrict__ weights, const float *__restrict__ mu, int K, int T,
@@ -92,9 +92,7 @@ __device__ __forceinline__ void desc_rows(const typename Vec4<IT>::type *__restr
 
     for (unsigned q = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); q < n; q += stride) { // wave-uniform
         unsigned row = q;
-        if constexpr (LIST) {
-            if (rows) row = (unsigned)rows[q];
-        }
+        if constexpr (LIST) row = (unsigned)rows[q];
         const typename Vec4<IT>::type *rp = nlist + (size_t)row * NN;
 
         // 1. this lane's slots: raw pair vector (virial), distance, type (-1: contributes nothing)

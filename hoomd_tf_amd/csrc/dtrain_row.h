@@ -1,4 +1,4 @@
-// The force-matching sweep's rows, written once for desc_train.hip (include/htf_desc_train.h) and bp.hip (include/htf_bp.h).
+// The force-matching sweep's rows (bp.hip, include/htf_bp.h).
 //
 // With the residual rho_i held fixed, d SSR / d theta = 2 sum_i d Q_i / d theta, Q_i = rho_i . F_i + rho_iE E_i, and
 // rho_i . F_i = grad_G E . Gdot is the network's derivative along Gdot_c = sum_j e_k'(r_ij) a_ij, a_ij = 2 (rho_i . t_ij) / r_ij.
@@ -18,39 +18,24 @@
 // past D (past H1) is skipped by a wave-uniform branch.
 //
 // No atomics and no memset: at the end the four waves of a block add their accumulators in wave order into the LDS that
-// held the weights, the block writes one partial [1 + P] to the scratch buffer, and dtrain_reduce_kernel (desc_train.hip)
+// held the weights, the block writes one partial [1 + P] to the scratch buffer, and dtrain_reduce_kernel (bp.hip)
 // adds the partials in a fixed order into accum.  The grid is a function of the number of work items alone, so two calls
 // on the same inputs give the same bits.
 //
-// Two compile-time switches serve bp.hip and are compiled out for desc_train.hip's kernel (desc_row.h has the same two):
+// Two compile-time switches beside the activation (desc_row.h has the same two):
 //   CUT   e_k -> fc(r) e_k, so e_k' a -> (c_der d fc + fc') e_k a; a slot at r >= rc is dropped where the slots are read.
-//   LIST  wave work item q handles row rows[q] (rows may still be null: row q): the labels and the prediction are read at
-//         the row, and q alone decides which wave and block accumulate it -- entry q is treated as row q of a batch of n.
+//   LIST  wave work item q handles row rows[q] instead of row q: the labels and the prediction are read at the row, and q
+//         alone decides which wave and block accumulate it -- entry q is treated as row q of a batch of n.
 #ifndef HTF_DTRAIN_ROW_H_
 #define HTF_DTRAIN_ROW_H_
-#include "htf_common.h"
-#include "htf_internal.h"
-#include "bp_cutoff.h"
+#include "desc_row.h"   // the limits, the activation and the weights' LDS layout are the evaluator's
 
 namespace htf {
-
-// desc_train.hip: accum[p] = the fixed-order sum of nparts partials of n floats (gradient entries doubled); nparts may be 0
-int dtrain_reduce_launch(const float *d_partials, unsigned nparts, unsigned n, float *d_accum, hipStream_t stream);
-
 namespace {
 
-constexpr int kDtMaxD = 64;    // channels: one per lane
-constexpr int kDtMaxH = 64;    // hidden units: one per lane
-constexpr int kDtSlots = 4;    // slots per lane: NN <= 256
 constexpr int kDtLines = 6;    // exchange lines per wave: G, Gdot, h1, hd1, zb2, zdb2
 constexpr unsigned kDtMaxBlocks = 512;   // partials the second kernel adds; each block stages the weights once
 constexpr unsigned kDtRowsPerBlock = 64; // rows a block takes before the grid grows: 16 per wave
-
-template <bool TANH>
-__device__ __forceinline__ float dtrain_act(float z) {   // (desc_row.h's desc_act: the prediction's own activation)
-    if constexpr (!TANH) return z;
-    return fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * z)), 1.0f);
-}
 
 // two exchange lines at once: every lane's writes are visible to every lane of the wave before the next read
 __device__ __forceinline__ void lines_publish(float *la, float *lb, unsigned lane, float a, float b) {
@@ -61,8 +46,6 @@ __device__ __forceinline__ void lines_publish(float *la, float *lb, unsigned lan
     __builtin_amdgcn_wave_barrier();
 }
 
-// floats of the weights in LDS: W1 [D][H1 + 1] | b1 | W2 [H1][H2 + 1] | b2 | W3 | b3   (as desc_row.h stages them)
-__host__ __device__ inline int dtrain_lds_weights(int D, int H1, int H2) { return D * (H1 + 1) + H1 + H1 * (H2 + 1) + H2 + H2 + 1; }
 __host__ __device__ inline unsigned dtrain_params(unsigned D, unsigned H1, unsigned H2) { return D * H1 + H1 + H1 * H2 + H2 + H2 + 1; }
 
 // acc[i] += va[i] * ca + vb[i] * cb for the 64 entries of two exchange lines; blocks of 16 past n are skipped (wave-uniform)
@@ -82,7 +65,7 @@ __device__ __forceinline__ void outer_accumulate(float (&acc)[64], const float *
     }
 }
 
-// n work items: rows 0 .. n - 1, or rows[0 .. n - 1] with LIST and a non-null list; one partial [1 + P] per block
+// n work items: rows 0 .. n - 1, or rows[0 .. n - 1] with LIST (rows is then not null); one partial [1 + P] per block
 template <bool TANH, bool CUT, bool LIST, typename IT>
 __device__ __forceinline__ void dtrain_rows(const typename Vec4<IT>::type *__restrict__ nlist, const int *__restrict__ rows, unsigned n,
                                             unsigned NN, const float *__restrict__ weights, const float *__restrict__ mu, int K, int T,
@@ -91,7 +74,7 @@ __device__ __forceinline__ void dtrain_rows(const typename Vec4<IT>::type *__res
     extern __shared__ float s_mem[];
     const int D = K * T;
     const int ld1 = H1 + 1, ld2 = H2 + 1;   // odd row strides: a column walk (lane a reads W2[a][b]) spreads over the banks
-    const int nw = dtrain_lds_weights(D, H1, H2);
+    const int nw = desc_lds_weights(D, H1, H2);
     const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     float *s_w = s_mem;
     float *s_mu = s_w + ((nw + 3) & ~3);
@@ -122,9 +105,7 @@ __device__ __forceinline__ void dtrain_rows(const typename Vec4<IT>::type *__res
 
     for (unsigned q = blockIdx.x * (blockDim.x >> 6) + wave; q < n; q += stride) { // wave-uniform
         unsigned row = q;
-        if constexpr (LIST) {
-            if (rows) row = (unsigned)rows[q];
-        }
+        if constexpr (LIST) row = (unsigned)rows[q];
         // 0. the residual (the same value in every lane)
         const float4 pr = pred[row];
         float lx, ly, lz, lw;
@@ -140,11 +121,11 @@ __device__ __forceinline__ void dtrain_rows(const typename Vec4<IT>::type *__res
 
         // 1. this lane's slots: distance, type (-1: contributes nothing), a = 2 (rho . t) / r
         const typename Vec4<IT>::type *rp = nlist + (size_t)row * NN;
-        float r[kDtSlots], a[kDtSlots];
-        float fc[kDtSlots], dfc[kDtSlots];   // (CUT only)
-        int ty[kDtSlots];
+        float r[kDescSlots], a[kDescSlots];
+        float fc[kDescSlots], dfc[kDescSlots];   // (CUT only)
+        int ty[kDescSlots];
 #pragma unroll
-        for (int t = 0; t < kDtSlots; ++t) {
+        for (int t = 0; t < kDescSlots; ++t) {
             const unsigned slot = t * 64 + lane;
             r[t] = 1.f;
             a[t] = 0.f;
@@ -174,9 +155,9 @@ __device__ __forceinline__ void dtrain_rows(const typename Vec4<IT>::type *__res
         float g_mine = 0.f, gd_mine = 0.f;
         for (int k = 0; k < K; ++k) {
             const float m = s_mu[k];
-            float e[kDtSlots], ed[kDtSlots];
+            float e[kDescSlots], ed[kDescSlots];
 #pragma unroll
-            for (int t = 0; t < kDtSlots; ++t) {
+            for (int t = 0; t < kDescSlots; ++t) {
                 e[t] = ed[t] = 0.f;
                 if ((unsigned)t < ns) {
                     const float d = r[t] - m;
@@ -194,7 +175,7 @@ __device__ __forceinline__ void dtrain_rows(const typename Vec4<IT>::type *__res
             for (int tt = 0; tt < T; ++tt) {
                 float p = 0.f, pd = 0.f;
 #pragma unroll
-                for (int t = 0; t < kDtSlots; ++t)
+                for (int t = 0; t < kDescSlots; ++t)
                     if ((unsigned)t < ns) {
                         p += ty[t] == tt ? e[t] : 0.f;
                         pd += ty[t] == tt ? ed[t] : 0.f;
@@ -217,7 +198,7 @@ __device__ __forceinline__ void dtrain_rows(const typename Vec4<IT>::type *__res
                 z1 = fmaf(sG[c], w, z1);
                 zd1 = fmaf(sGd[c], w, zd1);
             }
-            h1 = dtrain_act<TANH>(z1);
+            h1 = desc_act<TANH>(z1);
             s1 = TANH ? 1.0f - h1 * h1 : 1.0f;
         }
         lines_publish(sH, sHd, lane, h1, s1 * zd1);
@@ -229,7 +210,7 @@ __device__ __forceinline__ void dtrain_rows(const typename Vec4<IT>::type *__res
                 z2 = fmaf(sH[c], w, z2);
                 zd2 = fmaf(sHd[c], w, zd2);
             }
-            h2 = dtrain_act<TANH>(z2);
+            h2 = desc_act<TANH>(z2);
             s2 = TANH ? 1.0f - h2 * h2 : 1.0f;
             w3 = W3[lane];
         }
@@ -297,14 +278,14 @@ inline unsigned dtrain_grid(unsigned n) {
 }
 
 inline int dtrain_check(unsigned K, unsigned T, unsigned H1, unsigned H2) {
-    HTF_REQUIRE(K >= 2 && T >= 1 && K * T <= (unsigned)kDtMaxD && K <= (unsigned)kDtMaxD && T <= (unsigned)kDtMaxD,
-                "descriptor network: K = %u, n_types = %u outside 2 <= K, K * n_types <= %d", K, T, kDtMaxD);
-    HTF_REQUIRE(H1 >= 1 && H1 <= (unsigned)kDtMaxH && H2 >= 1 && H2 <= (unsigned)kDtMaxH,
-                "descriptor network: hidden widths %u, %u outside [1, %d]", H1, H2, kDtMaxH);
+    HTF_REQUIRE(K >= 2 && T >= 1 && K * T <= (unsigned)kDescMaxD && K <= (unsigned)kDescMaxD && T <= (unsigned)kDescMaxD,
+                "descriptor network: K = %u, n_types = %u outside 2 <= K, K * n_types <= %d", K, T, kDescMaxD);
+    HTF_REQUIRE(H1 >= 1 && H1 <= (unsigned)kDescMaxH && H2 >= 1 && H2 <= (unsigned)kDescMaxH,
+                "descriptor network: hidden widths %u, %u outside [1, %d]", H1, H2, kDescMaxH);
     return HTF_OK;
 }
 
-// what htf_dtrain_loss_grad and htf_bp_loss_grad check alike (everything but the row list and the cutoff)
+// what htf_bp_loss_grad checks of everything but the row list and the cutoff
 inline int dtrain_check_call(const void *nlist, int nlist_dtype, unsigned B, unsigned NN, unsigned K, unsigned T, unsigned H1,
                              unsigned H2, int activation, const float *weights, const float *mu, float gap, const void *labels,
                              int labels_dtype, const float *pred, const float *accum, const float *scratch) {
@@ -313,14 +294,14 @@ inline int dtrain_check_call(const void *nlist, int nlist_dtype, unsigned B, uns
     HTF_REQUIRE(labels_dtype == HTF_F32 || labels_dtype == HTF_F64, "descriptor network: unknown labels dtype %d", labels_dtype);
     const int rc = dtrain_check(K, T, H1, H2);
     if (rc != HTF_OK) return rc;
-    HTF_REQUIRE(NN <= 64u * kDtSlots, "descriptor network: NN %u > %d", NN, 64 * kDtSlots);
+    HTF_REQUIRE(NN <= 64u * kDescSlots, "descriptor network: NN %u > %d", NN, 64 * kDescSlots);
     HTF_REQUIRE(gap > 0.0f, "descriptor network: the centre spacing must be positive (gap = %g)", (double)gap);
     HTF_REQUIRE(activation == HTF_ACT_LINEAR || activation == HTF_ACT_TANH, "descriptor network: unknown activation %d", activation);
     return HTF_OK;
 }
 
 inline size_t dtrain_lds(unsigned K, unsigned T, unsigned H1, unsigned H2) {
-    return ((((size_t)dtrain_lds_weights((int)(K * T), (int)H1, (int)H2) + 3) & ~(size_t)3) + ((K + 3) & ~3u) + 4 * kDtLines * 64) * sizeof(float);
+    return ((((size_t)desc_lds_weights((int)(K * T), (int)H1, (int)H2) + 3) & ~(size_t)3) + ((K + 3) & ~3u) + 4 * kDtLines * 64) * sizeof(float);
 }
 
 } // namespace

@@ -17,8 +17,6 @@
 #include "htf_cg.h"
 #include "htf_geom.h"
 #include "htf_nlist.h"
-#include "htf_desc.h"
-#include "htf_desc_train.h"
 #include "htf_bp.h"
 
 namespace py = pybind11;
@@ -175,17 +173,7 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
     X(htf_nlist_cells_scratch_words) \
     X(htf_nlist_cells_forward)
 
-// include/htf_desc.h: the descriptor network (_lib.DESC_PROTOTYPES)
-#define HTF_DESC_FUNCTIONS(X) \
-    X(htf_desc_forces) \
-    X(htf_desc_descriptor)
-
-// include/htf_desc_train.h: force matching for the descriptor network (_lib.DESC_TRAIN_PROTOTYPES)
-#define HTF_DESC_TRAIN_FUNCTIONS(X) \
-    X(htf_dtrain_scratch_floats) \
-    X(htf_dtrain_loss_grad)
-
-// include/htf_bp.h: the descriptor network with a cutoff and over a row list (_lib.BP_PROTOTYPES)
+// include/htf_bp.h: the descriptor network (_lib.BP_PROTOTYPES)
 #define HTF_BP_FUNCTIONS(X) \
     X(htf_bp_forces) \
     X(htf_bp_descriptor) \
@@ -205,8 +193,6 @@ PYBIND11_MODULE(_htf_abi, m) {
     HTF_CG_FUNCTIONS(X)
     HTF_GEOM_FUNCTIONS(X)
     HTF_NLIST_FUNCTIONS(X)
-    HTF_DESC_FUNCTIONS(X)
-    HTF_DESC_TRAIN_FUNCTIONS(X)
     HTF_BP_FUNCTIONS(X)
 #undef X
 }

@@ -292,7 +292,7 @@ class PairMLP:
 
 
 class DescriptorMLP:
-    """A descriptor network of Behler-Parrinello / SchNet form, evaluated in one HIP kernel (include/htf_desc.h).
+    """A descriptor network of Behler-Parrinello / SchNet form, evaluated in one HIP kernel (include/htf_bp.h).
 
     Called on the neighbor list it returns the symbolic per-particle energy ``E_i``; ``compute_nlist_forces(nlist, E)``
     gives the forces ``2 sum_j dE_i/dx_ij`` with ``E_i`` in column 3, and the generic route's virial when asked::
@@ -308,7 +308,7 @@ class DescriptorMLP:
     each term with its own ``compute_nlist_forces`` and add the forces.
 
     ``r_cut=rc`` multiplies every Gaussian by the cosine cutoff ``fc(r) = 0.5 (cos(pi r / rc) + 1)`` for ``r < rc`` and 0
-    beyond (include/htf_bp.h), so that a neighbor entering or leaving at ``rc`` changes neither energy nor force; ``rc``
+    beyond, so that a neighbor entering or leaving at ``rc`` changes neither energy nor force; ``rc``
     (rounded to fp32) should not exceed the ``r_cut`` of the neighbor list, which is not checked.  ``None``: no cutoff.
     ``n_species=S`` keeps one network per particle species, Behler-Parrinello's one network per element: ``w`` holds S
     networks of P floats, network ``s`` at ``w[s P:(s + 1) P]`` initialised from ``mlp_params(seed + s, ...)``, and row ``i`` is
@@ -317,7 +317,7 @@ class DescriptorMLP:
     outside ``[0, S)`` raises; with ``S = 1`` they are ignored.  Each call partitions the rows by species on the device
     (one read-back of the S counts, cached while the same species tensor is passed) and launches once per species present.
 
-    ``trainable=True`` makes the layer learn by force matching (include/htf_desc_train.h): under ``tfcompute.attach(...,
+    ``trainable=True`` makes the layer learn by force matching (htf_bp_loss_grad): under ``tfcompute.attach(...,
     train=True)`` every batch is one ``loss_gradient`` sweep -- the sum of squared residuals of (F_i, E_i) against the
     labels and its gradient with respect to ``w``, one pass over the pair vectors -- and one optimizer step on ``w``, on
     the device.  ``loss_gradient`` is also the offline entry: with ``iter_from_trajectory`` and ``ops.optimizer_step`` on
@@ -469,11 +469,6 @@ class DescriptorMLP:
         out = torch.empty((B, 4), dtype=x.dtype, device=x.device)
         v = torch.empty((B, 3, 3), dtype=x.dtype, device=x.device) if virial else None
         act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
-        if self.r_cut is None and self.n_species == 1:
-            check(lib.htf_desc_forces(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, self.w.data_ptr(),
-                                      self.mu.data_ptr(), float(self.gap), out.data_ptr(), ops._dt(out),
-                                      v.data_ptr() if v is not None else None, ops._stream(x)))
-            return (out, v) if virial else out
         launches, rows = self._launches(species, x)
         for _, d_rows, n_rows, d_w in launches:   # every row is in exactly one list: no memset
             check(lib.htf_bp_forces(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, d_w,
@@ -483,7 +478,7 @@ class DescriptorMLP:
         return (out, v) if virial else out
 
     def loss_gradient(self, x, labels, pred=None, accum=None, species=None):
-        """One force-matching sweep (htf_dtrain_loss_grad) over a pair-vector tensor ``x`` [B, NN, 4] (fp32 or fp64) and
+        """One force-matching sweep (htf_bp_loss_grad) over a pair-vector tensor ``x`` [B, NN, 4] (fp32 or fp64) and
         ``labels`` [B, 4] (fp32 or fp64): returns ``accum`` [1 + P] fp32 on the device, {sum of squared residuals of
         (F_i, E_i), its gradient with respect to ``w``} -- what ``ops.optimizer_step(w, accum, 1 / (4 B), ...)`` consumes for
         Keras' MeanSquaredError.  ``pred`` [B, 4] fp32: the layer's ``forces(x)`` at the current weights, evaluated here
@@ -509,13 +504,6 @@ class DescriptorMLP:
         if accum.numel() != S * (1 + P) or accum.device != x.device:
             raise ValueError("DescriptorMLP: accum must hold %d floats on %s" % (S * (1 + P), x.device))
         act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
-        if self.r_cut is None and S == 1:
-            scratch = torch.empty(int(lib.htf_dtrain_scratch_floats(B, self.K, self.n_types, self.H1, self.H2)), dtype=torch.float32,
-                                  device=x.device)
-            check(lib.htf_dtrain_loss_grad(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, self.w.data_ptr(),
-                                           self.mu.data_ptr(), float(self.gap), labels.data_ptr(), ops._dt(labels), pred.data_ptr(),
-                                           accum.data_ptr(), scratch.data_ptr(), ops._stream(x)))
-            return accum
         launches, rows = self._launches(species, x)
         # one scratch buffer for the largest species: the launches run one after the other on the stream
         scratch = torch.empty(max(1, int(lib.htf_bp_scratch_floats(max([n for _, _, n, _ in launches] or [0]), self.K, self.n_types,
@@ -538,12 +526,8 @@ class DescriptorMLP:
         x = simmodel._as_nlist(nlist).tensor
         B, NN = self._check(x)
         out = torch.empty((B, self.D), dtype=x.dtype, device=x.device)
-        if self.r_cut is None:
-            check(lib.htf_desc_descriptor(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.mu.data_ptr(), float(self.gap),
-                                          out.data_ptr(), ops._dt(out), ops._stream(x)))
-        else:
-            check(lib.htf_bp_descriptor(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.mu.data_ptr(), float(self.gap),
-                                        out.data_ptr(), ops._dt(out), float(self.r_cut), ops._stream(x)))
+        check(lib.htf_bp_descriptor(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.mu.data_ptr(), float(self.gap),
+                                    out.data_ptr(), ops._dt(out), float(self.r_cut or 0.0), ops._stream(x)))
         simmodel._trace_log().append({"op": "descriptor"})   # (no replay: a model calling it keeps the eager path)
         return out
 

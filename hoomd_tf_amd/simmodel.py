@@ -1426,7 +1426,7 @@ class MLPEnergy(PairEnergy):
 
 class DescriptorEnergy(PairEnergy):
     """DescriptorMLP(nlist): the per-particle energy [N] of the descriptor network.  compute_nlist_forces evaluates it in one
-    kernel (htf_desc_forces) and keeps the step eager.  It does not combine with other energies: arithmetic raises, so a sum
+    kernel (htf_bp_forces) and keeps the step eager.  It does not combine with other energies: arithmetic raises, so a sum
     the kernel cannot form never reaches the forces.  ``species``: the tensor the layer reads the particles' own species from
     (one network per species, DescriptorMLP(n_species=...)), None for a layer of one network."""
     reduced = True

@@ -6,7 +6,7 @@ double backward of tests/test_gpu_desc_train.py with fc multiplied in:
     fc(r) = 0.5 (cos(pi r / rc) + 1) for r < rc, 0 beyond;   G_i[t*K + k] = sum_j live_ij [t_ij = t] fc(r_ij) exp(-(r_ij - mu_k)^2 / gap)
 
 at those files' bounds (2e-5 of the largest reference value; 2e-4 of the largest gradient entry).  The row list and the
-species are checked bit for bit against a layer of one network on the same rows (include/htf_bp.h, contracts (a) - (c))."""
+species are checked bit for bit against a layer of one network on the same rows (include/htf_bp.h, contracts (b) and (c))."""
 import math
 
 import numpy as np
@@ -183,42 +183,87 @@ def test_energy_is_continuous_at_the_cutoff(htf, cuda, seed):
     assert (got_plain[rows] > 0.5 * jump[rows]).all()
 
 
-# ------------------------------------------------------------------------------------------------ 4. default bits (contract a)
-@pytest.mark.parametrize("NN", [37, 256])
-def test_null_list_and_no_cutoff_give_the_default_layers_bits(htf, cuda, NN):
+# ------------------------------------------------------------------------------------------------ 4. the row list (contract b)
+def _pairs(rng, B, NN, dtype):
+    """random_nlist without its loop over the rows: live neighbors of two types at 0.3 <= r <= 3.2 (both sides of 2.6), padding."""
+    v = rng.standard_normal((B, NN, 3))
+    v *= rng.uniform(0.3, 3.2, (B, NN, 1)) / np.linalg.norm(v, axis=2, keepdims=True)
+    nl = np.concatenate([v, rng.integers(0, 2, (B, NN, 1)).astype(np.float64)], axis=2)
+    nl[np.arange(NN)[None, :] >= rng.binomial(NN, 0.75, B)[:, None]] = 0.0
+    return torch.from_numpy(nl).to(dtype)
+
+
+# the sizes follow the launch geometry (csrc/desc_row.h desc_grid, csrc/dtrain_row.h dtrain_grid): fewer rows than a block
+# has waves, partial slots (NN = 37) and all four (256), several blocks, one row past the forces grid's single pass
+# (2048 blocks x 4 waves) and one block's worth past the sweep grid's (512 blocks x 64 rows)
+FORCES_GRID_ROWS, SWEEP_BLOCKS, SWEEP_BLOCK_ROWS = 2048 * 4, 512, 64
+LIST_CASES = ([(B, NN, torch.float32, "small") for B in (1, 3, 5) for NN in (37, 256)]
+              + [(300, NN, dt, "wide") for NN in (37, 256) for dt in (torch.float32, torch.float64)]
+              + [(FORCES_GRID_ROWS + 3, 16, torch.float32, "small"), (SWEEP_BLOCKS * SWEEP_BLOCK_ROWS + 3, 16, torch.float32, "small")])
+NETWORKS = {"small": dict(K=8, n_types=2, H1=8, H2=8), "wide": dict(K=16, n_types=2, H1=24, H2=20)}
+
+
+def test_a_row_list_changes_which_rows_are_evaluated_never_a_bit(htf, cuda):
+    """Every comparison is torch.equal.  Forces and virial into NaN-filled outputs: the identity list and the reversed list
+    give the call without a list; every third row gives it on the listed rows and leaves the others NaN.  The sweep: the
+    identity list gives the call without a list (a reordered one need not: the partial sums follow q).  The descriptor entry
+    at r_cut = 0 is the layer without a cutoff.  The scratch size is dtrain_grid(n) partials of 1 + P."""
     from hoomd_tf_amd import _lib, ops
     lib, check = _lib.lib, _lib.check
-    B = 300
-    rng = np.random.default_rng(NN)
-    nl, _ = random_nlist(rng, B, NN, fill=0.75, rmin=0.3, rmax=3.4, ntypes=2, dtype=np.float32)
-    x = torch.from_numpy(nl).to(cuda)
-    labels = torch.from_numpy(0.05 * rng.standard_normal((B, 4))).float().to(cuda)
-    for activation in ("tanh", "linear"):
-        lay = _layer(htf, K=16, n_types=2, H1=24, H2=20, activation=activation, trainable=True)
-        act = _lib.ACT_TANH if activation == "tanh" else _lib.ACT_LINEAR
-        net_args = (x.data_ptr(), ops._dt(x), B, NN, lay.K, lay.n_types, lay.H1, lay.H2, act, lay.w.data_ptr(), lay.mu.data_ptr(),
-                    float(lay.gap))
-        f, v = lay.forces(x, virial=True)
-        f2, v2 = torch.full_like(f, float("nan")), torch.full_like(v, float("nan"))
-        check(lib.htf_bp_forces(*net_args, f2.data_ptr(), ops._dt(f2), v2.data_ptr(), None, B, 0.0, ops._stream(x)))
-        assert torch.equal(f2, f) and torch.equal(v2, v)
-        f3 = torch.full_like(f, float("nan"))
-        check(lib.htf_bp_forces(*net_args, f3.data_ptr(), ops._dt(f3), None, None, B, 0.0, ops._stream(x)))
-        assert torch.equal(f3, f)
-        G = lay.descriptor(x)
-        G2 = torch.full_like(G, float("nan"))
-        check(lib.htf_bp_descriptor(x.data_ptr(), ops._dt(x), B, NN, lay.K, lay.n_types, lay.mu.data_ptr(), float(lay.gap),
-                                    G2.data_ptr(), ops._dt(G2), 0.0, ops._stream(x)))
-        assert torch.equal(G2, G)
-        pred = f.contiguous()
-        accum = lay.loss_gradient(x, labels, pred=pred)
-        n = int(lib.htf_bp_scratch_floats(B, lay.K, lay.n_types, lay.H1, lay.H2))
-        assert n == int(lib.htf_dtrain_scratch_floats(B, lay.K, lay.n_types, lay.H1, lay.H2))
-        scratch = torch.empty(n, dtype=torch.float32, device=cuda)
-        accum2 = torch.full_like(accum, float("nan"))
-        check(lib.htf_bp_loss_grad(*net_args, labels.data_ptr(), ops._dt(labels), pred.data_ptr(), accum2.data_ptr(),
-                                   scratch.data_ptr(), None, B, 0.0, ops._stream(x)))
-        assert torch.equal(accum2, accum)
+    assert [c[0] for c in LIST_CASES[-2:]] == [8195, 32771]
+    nan = float("nan")
+    for B, NN, dtype, size in LIST_CASES:
+        rng = np.random.default_rng(B + NN)
+        x = _pairs(rng, B, NN, dtype).to(cuda)
+        labels = torch.from_numpy(0.05 * rng.standard_normal((B, 4))).float().to(cuda)
+        lists = {"identity": torch.arange(B, dtype=torch.int32, device=cuda),
+                 "reversed": torch.arange(B - 1, -1, -1, dtype=torch.int32, device=cuda),
+                 "third": torch.arange(1, B, 3, dtype=torch.int32, device=cuda)}
+        assert len(lists["third"]) < B
+        listed = torch.zeros(B, dtype=torch.bool, device=cuda)
+        listed[lists["third"].long()] = True
+        for r_cut in (None, 2.6):
+            for activation in ("tanh", "linear"):
+                kw = {} if r_cut is None else {"r_cut": r_cut}
+                lay = _layer(htf, activation=activation, trainable=True, **NETWORKS[size], **kw)
+                rc = float(lay.r_cut or 0.0)
+                act = _lib.ACT_TANH if activation == "tanh" else _lib.ACT_LINEAR
+                net_args = (x.data_ptr(), ops._dt(x), B, NN, lay.K, lay.n_types, lay.H1, lay.H2, act, lay.w.data_ptr(),
+                            lay.mu.data_ptr(), float(lay.gap))
+                what = "B=%d NN=%d %s r_cut=%s %s" % (B, NN, dtype, r_cut, activation)
+                f, v = lay.forces(x, virial=True)
+                assert torch.isfinite(f).all() and torch.isfinite(v).all(), what
+                for name, rows in lists.items():
+                    f2, v2 = torch.full_like(f, nan), torch.full_like(v, nan)
+                    check(lib.htf_bp_forces(*net_args, f2.data_ptr(), ops._dt(f2), v2.data_ptr(), rows.data_ptr() if len(rows) else None,
+                                            len(rows), rc, ops._stream(x)))
+                    f3 = torch.full_like(f, nan)
+                    check(lib.htf_bp_forces(*net_args, f3.data_ptr(), ops._dt(f3), None, rows.data_ptr() if len(rows) else None,
+                                            len(rows), rc, ops._stream(x)))
+                    if name == "third":
+                        assert torch.equal(f2[listed], f[listed]) and torch.equal(v2[listed], v[listed]), (what, name)
+                        assert torch.isnan(f2[~listed]).all() and torch.isnan(v2[~listed]).all() and torch.isnan(f3[~listed]).all()
+                        assert torch.equal(f3[listed], f[listed]), (what, name)
+                    else:
+                        assert torch.equal(f2, f) and torch.equal(v2, v) and torch.equal(f3, f), (what, name)
+                # the sweep
+                pred = f.to(torch.float32).contiguous()
+                accum = lay.loss_gradient(x, labels, pred=pred)
+                assert torch.isfinite(accum).all() and accum[1:].abs().max().item() > 0, what
+                n = int(lib.htf_bp_scratch_floats(B, lay.K, lay.n_types, lay.H1, lay.H2))
+                assert n == min(-(-B // SWEEP_BLOCK_ROWS), SWEEP_BLOCKS) * (1 + lay.P), what
+                scratch = torch.empty(n, dtype=torch.float32, device=cuda)
+                accum2 = torch.full_like(accum, nan)
+                check(lib.htf_bp_loss_grad(*net_args, labels.data_ptr(), ops._dt(labels), pred.data_ptr(), accum2.data_ptr(),
+                                           scratch.data_ptr(), lists["identity"].data_ptr(), B, rc, ops._stream(x)))
+                assert torch.equal(accum2, accum), what
+            # the descriptor does not see the network: once per cutoff
+            if r_cut is None:
+                G = lay.descriptor(x)
+                G2 = torch.full_like(G, nan)
+                check(lib.htf_bp_descriptor(x.data_ptr(), ops._dt(x), B, NN, lay.K, lay.n_types, lay.mu.data_ptr(), float(lay.gap),
+                                            G2.data_ptr(), ops._dt(G2), 0.0, ops._stream(x)))
+                assert torch.equal(G2, G) and torch.isfinite(G).all(), what
 
 
 # ------------------------------------------------------------------------------------------------ 5. species, forces (contract b)

@@ -1,4 +1,4 @@
-"""htf.DescriptorMLP on the MI355X (csrc/desc_mlp.hip) against an fp64 torch-autograd restatement of its definition:
+"""htf.DescriptorMLP on the MI355X (csrc/bp.hip over desc_row.h) against an fp64 torch-autograd restatement of its definition:
 
     r_ij = sqrt(sum_c (x_ij,c + 1e-7)^2), live_ij = r_ij > 3e-6, t_ij = 0 (n_types = 1) or rint(nlist[i, j, 3])
     G_i[t*K + k] = sum_j live_ij [t_ij = t] exp(-(r_ij - mu_k)^2 / gap)

@@ -1,4 +1,4 @@
-"""Force matching for htf.DescriptorMLP on the MI355X (csrc/desc_train.hip) against torch's fp64 double backward of the layer's
+"""Force matching for htf.DescriptorMLP on the MI355X (csrc/bp.hip over dtrain_row.h) against torch's fp64 double backward of the layer's
 definition (the reference() construction of tests/test_gpu_desc.py, made differentiable in the weights):
 
     pred_i = (F_i, E_i),  SSR = sum_i |pred_i - labels_i|^2,  accum = {SSR, d SSR / d theta},  theta = W1|b1|W2|b2|W3|b3.

@@ -1,4 +1,4 @@
-"""Times htf.DescriptorMLP (csrc/desc_mlp.hip) against the same network written with RBFExpansion and Dense on the torch route.
+"""Times htf.DescriptorMLP (csrc/bp.hip over desc_row.h) against the same network written with RBFExpansion and Dense on the torch route.
 
 For each shape: a random [N, NN, 4] fp32 pair-vector tensor (60..NN live neighbors per row at 0.8 <= r <= 3.2, zero padding),
 the layer with K channels on [0, 3], H1 = H2 hidden units, tanh.  Timed: compute_nlist_forces(nlist, layer(nlist)) (the

@@ -6,8 +6,8 @@ Usage:  python tools/desc_train_probe.py [--n 131072] [--nn 128] [--iters 20] [-
 
 N rows x NN slots, K = 32 channels, 64 x 64 tanh, one type.  HIP events around each launch, the median of --iters launches
 after --warmup:
-  (a) htf_desc_forces            DescriptorMLP.forces(x)
-  (b) the training sweep         DescriptorMLP.loss_gradient(x, labels, pred=...): dtrain_sweep_kernel + dtrain_reduce_kernel
+  (a) htf_bp_forces              DescriptorMLP.forces(x)
+  (b) the training sweep         DescriptorMLP.loss_gradient(x, labels, pred=...): bp_sweep_kernel + dtrain_reduce_kernel
   (c) one training step of the same network on the generic torch route: RBF expansion, masked sum over the neighbors and
       three dense layers in plain torch (what RBFExpansion + Dense compute), forces by autograd with create_graph, the mean
       squared error over [N, 4], backward, one SGD step -- in row chunks of --chunk whose gradients add up, so that the

@@ -71,7 +71,8 @@ MIRROR_MAX = 4
 class StepEpilogue(C.Structure):
     """htfs_step_epilogue: the stand-in integrator (and a brick's halo pack) as the one-kernel step's epilogue."""
     _fields_ = [("d_vel", C.c_void_p), ("d_pos_next", C.c_void_p), ("dtype", C.c_int), ("dt", C.c_double), ("box", Box),
-                ("brick", C.c_void_p), ("d_row_slots", C.c_void_p), ("d_halo_send", C.c_void_p), ("d_ghost_direct", C.c_void_p)]
+                ("brick", C.c_void_p), ("d_row_slots", C.c_void_p), ("d_halo_send", C.c_void_p), ("d_ghost_direct", C.c_void_p),
+                ("d_mail_src", C.c_void_p), ("h_mail_dst", C.c_void_p)]
 
 
 MBOX_MAX_MSG, MBOX_MAX_RANKS, IPC_HANDLE_BYTES = 8, 64, 64   # include/htf_standin.h HTFS_MBOX_MAX_MSG / _MAX_RANKS, HTFS_IPC_HANDLE_BYTES
@@ -220,7 +221,7 @@ STANDIN_PROTOTYPES = {
     "htfs_brick_pack_halo_peer": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "htfs_brick_unpack_halo": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "htfs_set_step_epilogue": (_i, [_vp, _i, _vp, _vp]),
-    "htfs_use_step_epilogue": (_i, [_vp, _i]),
+    "htfs_use_step_epilogue": (_i, [_vp, _i, _i]),
     "htfs_brick_row_slots": (_i, [_vp, _vp, _vp, _vp]),
     "htfs_shared_alloc": (_i, [_sz, _i, _vp]),
     "htfs_shared_free": (_i, [_vp]),
@@ -240,6 +241,12 @@ STANDIN_PROTOTYPES = {
     "htfs_build_nlist": (_i, [C.POINTER(Nlist), _vp, _i, _u, _vp]),
     "htfs_rebuild_nlist": (_i, [C.POINTER(Nlist), _vp, _i, _u, _u, _i, _vp]),
     "htfs_check_rebuild_nlist": (_i, [C.POINTER(Nlist), _vp, _i, _u, _u, _i, _vp, _d, _vp, _vp, _vp]),
+}
+
+# the check step without a check launch (include/htf_step_check.h; standin.FusedStep, CellNlist)
+STEP_CHECK_PROTOTYPES = {
+    "htfs_nve_step_check": (_i, [_vp, _vp, _vp, _i, _u, _d, C.POINTER(Box), C.POINTER(Nlist), _vp, _vp]),
+    "htfs_rebuild_nlist_gated": (_i, [C.POINTER(Nlist), _vp, _i, _u, _u, _i, _vp, _d, _vp, _vp, _i, _vp]),
 }
 
 # coarse-grained mapping ops (include/htf_cg.h): center_of_mass, compute_nlist (hoomd_tf_amd/cgmap.py)
@@ -273,7 +280,7 @@ BP_PROTOTYPES = {
 }
 
 # every table above: what the ctypes and the pybind11 binding both declare
-ALL_PROTOTYPES = tuple((name, proto) for table in (PROTOTYPES, STANDIN_PROTOTYPES, CG_PROTOTYPES, GEOM_PROTOTYPES, NLIST_PROTOTYPES,
+ALL_PROTOTYPES = tuple((name, proto) for table in (PROTOTYPES, STANDIN_PROTOTYPES, STEP_CHECK_PROTOTYPES, CG_PROTOTYPES, GEOM_PROTOTYPES, NLIST_PROTOTYPES,
                                                    BP_PROTOTYPES) for name, proto in table.items())
 
 

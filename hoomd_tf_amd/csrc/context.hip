@@ -93,6 +93,9 @@ struct htf_ctx {
     bool epilogue_ok[HTFS_EPILOGUE_SLOTS] = {false, false};
     int epilogue_level[HTFS_EPILOGUE_SLOTS] = {0, 0};          // 1: the integrator alone, 2: + a brick's halo messages
     int epilogue_slot = -1;                                     // what the next compute call carries
+    void *d_epilogue_mail[HTFS_EPILOGUE_SLOTS] = {nullptr, nullptr}; // the same descriptors with the mail fields set (nullptr: none)
+    bool epilogue_has_mail[HTFS_EPILOGUE_SLOTS] = {false, false};
+    bool epilogue_mail = false;                                 // ... with the slot's mail
 };
 
 static hipEvent_t next_event(htf_ctx *c) {
@@ -434,6 +437,8 @@ extern "C" void htf_destroy(htf_ctx *ctx) {
     if (ctx->flag) (void)hipFree(ctx->flag);
     for (void *d : ctx->d_epilogue)
         if (d) (void)hipFree(d);
+    for (void *d : ctx->d_epilogue_mail)
+        if (d) (void)hipFree(d);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     delete ctx;
 }
@@ -444,6 +449,7 @@ extern "C" int htf_set_potential(htf_ctx *ctx, const htf_potential *pot) {
     ctx->pot = pot;
     // (a registered step epilogue was judged against the potential it was registered under: register it again)
     ctx->epilogue_slot = -1;
+    ctx->epilogue_mail = false;
     for (bool &ok : ctx->epilogue_ok) ok = false;
     return HTF_OK;
 }
@@ -532,7 +538,7 @@ static int compute_rows(htf_ctx *ctx, unsigned timestep, const htf_hoomd_arrays 
             if (cfg.check_nlist) HTF_CHECK_HIP(hipMemsetAsync(ctx->flag, 0, sizeof(unsigned), s));
             void *fo = (char *)a->force + (size_t)offset * 4 * ssz;
             // (the epilogue rides on this launch only: the request is this thread's, cleared behind the call)
-            step_epilogue_request() = ctx->epilogue_slot >= 0 ? ctx->d_epilogue[ctx->epilogue_slot] : nullptr;
+            step_epilogue_request() = ctx->epilogue_slot >= 0 ? (ctx->epilogue_mail ? ctx->d_epilogue_mail : ctx->d_epilogue)[ctx->epilogue_slot] : nullptr;
             step_epilogue_level() = ctx->epilogue_slot >= 0 ? ctx->epilogue_level[ctx->epilogue_slot] : 0;
             rc = fused_forces_impl(ctx->pot->pp, a->pos, cfg.scalar_dtype, N, cfg.nneighs, offset, n, &a->box, a->n_neigh,
                                    a->nlist, a->head_list, cfg.r_cut, fo, cfg.scalar_dtype,
@@ -660,6 +666,8 @@ extern "C" int htfs_set_step_epilogue(htf_ctx *ctx, int slot, const htfs_step_ep
     HTF_REQUIRE(ep->d_vel && ep->d_pos_next && (ep->dtype == HTF_F32 || ep->dtype == HTF_F64), "htfs_set_step_epilogue: null pointer or bad dtype");
     HTF_REQUIRE(ep->brick == nullptr || (ep->d_row_slots && (ep->d_halo_send || ep->d_ghost_direct)),
                 "htfs_set_step_epilogue: a brick needs its row slots and a destination for the messages");
+    HTF_REQUIRE((ep->d_mail_src == nullptr) == (ep->h_mail_dst == nullptr) && ((uintptr_t)ep->d_mail_src & 3) == 0 && ((uintptr_t)ep->h_mail_dst & 7) == 0,
+                "htfs_set_step_epilogue: the mail needs a source and an 8-byte aligned destination");
     const htf_config &cfg = ctx->cfg;
     const htf_potential *pot = ctx->pot;
     // honoured by: the one-kernel route of LJModel / WCARepulsion on fp32 positions (the forms compiled with an epilogue), no virial
@@ -669,15 +677,26 @@ extern "C" int htfs_set_step_epilogue(htf_ctx *ctx, int slot, const htfs_step_ep
                     (pot->pp.kind == HTF_POT_LJ || pot->pp.kind == HTF_POT_WCA) && // (the forms compiled with an epilogue: fused_eval.hip)
                     (ep->brick == nullptr || !ep->brick->halo_wrap);                // (a replica brick on the GLOBAL cell grid wraps its messages)
     ctx->epilogue_ok[slot] = false;
+    ctx->epilogue_has_mail[slot] = false;
     if (ok) {
+        // (two descriptors per slot: the plain one, and -- when the caller names a mail -- one that carries it)
+        const bool mail = ep->d_mail_src != nullptr;
         if (ctx->d_epilogue[slot] == nullptr) HTF_CHECK_HIP(hipMalloc(&ctx->d_epilogue[slot], sizeof(StepEpilogue<double>)));
+        if (mail && ctx->d_epilogue_mail[slot] == nullptr) HTF_CHECK_HIP(hipMalloc(&ctx->d_epilogue_mail[slot], sizeof(StepEpilogue<double>)));
         if (ep->dtype == HTF_F64) {
-            const StepEpilogue<double> e = make_step_epilogue<double>(ep);
+            StepEpilogue<double> e = make_step_epilogue<double>(ep);
             HTF_CHECK_HIP(hipMemcpy(ctx->d_epilogue[slot], &e, sizeof e, hipMemcpyHostToDevice));
+            e.mail_src = ep->d_mail_src;
+            e.mail_dst = ep->h_mail_dst;
+            if (mail) HTF_CHECK_HIP(hipMemcpy(ctx->d_epilogue_mail[slot], &e, sizeof e, hipMemcpyHostToDevice));
         } else {
-            const StepEpilogue<float> e = make_step_epilogue<float>(ep);
+            StepEpilogue<float> e = make_step_epilogue<float>(ep);
             HTF_CHECK_HIP(hipMemcpy(ctx->d_epilogue[slot], &e, sizeof e, hipMemcpyHostToDevice));
+            e.mail_src = ep->d_mail_src;
+            e.mail_dst = ep->h_mail_dst;
+            if (mail) HTF_CHECK_HIP(hipMemcpy(ctx->d_epilogue_mail[slot], &e, sizeof e, hipMemcpyHostToDevice));
         }
+        ctx->epilogue_has_mail[slot] = mail;
         ctx->epilogue_ok[slot] = true;
         ctx->epilogue_level[slot] = ep->brick != nullptr ? 2 : 1;
     }
@@ -685,12 +704,14 @@ extern "C" int htfs_set_step_epilogue(htf_ctx *ctx, int slot, const htfs_step_ep
     return HTF_OK;
 }
 
-extern "C" int htfs_use_step_epilogue(htf_ctx *ctx, int slot) {
+extern "C" int htfs_use_step_epilogue(htf_ctx *ctx, int slot, int mail) {
     using namespace htf;
     HTF_REQUIRE(ctx, "htfs_use_step_epilogue: null context");
     HTF_REQUIRE(slot >= -1 && slot < HTFS_EPILOGUE_SLOTS, "htfs_use_step_epilogue: slot %d", slot);
     HTF_REQUIRE(slot < 0 || ctx->epilogue_ok[slot], "htfs_use_step_epilogue: slot %d holds no descriptor this context honours", slot);
+    HTF_REQUIRE(!mail || (slot >= 0 && ctx->epilogue_has_mail[slot]), "htfs_use_step_epilogue: slot %d was registered without a mail", slot);
     ctx->epilogue_slot = slot;
+    ctx->epilogue_mail = mail != 0;
     return HTF_OK;
 }
 

@@ -698,6 +698,7 @@ __global__ __launch_bounds__(256, sizeof(PT) == 8 ? HTF_TAILS_MINB_F64 : 1) void
     const unsigned *__restrict__ head_list, PT rmaxsq, void *__restrict__ force, int out_f64, PotParams pin,
     unsigned *__restrict__ check_count, float4 *__restrict__ positions_out, float4 *__restrict__ dest,
     unsigned *__restrict__ counts_io, const StepEpilogue<PT> *__restrict__ ep) {
+    if constexpr (EP != 0) step_epilogue_mail<PT>(ep);
     const PotParams p = resolve_theta<KIND>(pin);
     const unsigned lane = threadIdx.x & 63u;
     // (one wave per group of R rows.  Round 3, measured: the same body under a grid-stride loop, waves persistent at 4 ... 32
@@ -738,6 +739,7 @@ __global__ __launch_bounds__(256) void fused_forces_rows2_kernel(
     const unsigned *__restrict__ head_list, PT rmaxsq, void *__restrict__ force, int out_f64, PotParams pin,
     unsigned *__restrict__ check_count, float4 *__restrict__ positions_out, float4 *__restrict__ dest,
     unsigned *__restrict__ counts_io, const StepEpilogue<PT> *__restrict__ ep) {
+    if constexpr (EP != 0) step_epilogue_mail<PT>(ep);
     fused_forces_rows2_body<KIND, STORE, R, PT, EP>(pos, N, NN, offset, batch, box, n_neigh, nlist, head_list, rmaxsq, force, out_f64, pin,
                                                     check_count, positions_out, dest, counts_io, EP ? ep : nullptr);
 }

@@ -48,7 +48,24 @@ struct StepEpilogue {
     int n_msg = 0, halo_wrap = 0;
     unsigned ghost_off[8], ghost_off_opp[8]; // (message m lands at ghost_off[n_msg - 1 - m] of a rank that is its own neighbor)
     T shift[8][3];
+    // two status words an earlier launch on the stream left on the device -> pinned host memory (htfs_step_epilogue's mail: a
+    // device-decided list's [largest row, rebuilds] on the force launch of a check step).  mail_src == nullptr: nothing to carry
+    const unsigned *mail_src = nullptr;
+    unsigned *mail_dst = nullptr; // 8-byte aligned
 };
+
+// The mail of a launch that carries an epilogue: ONE lane of the grid reads the two words past the caches and stores them as ONE
+// 8-byte word -- never torn -- behind a system-scope fence.  At the head of the kernel: the words travel while the rows are evaluated
+// and the registers it uses are free again before the rows need them.
+template <typename T>
+__device__ __forceinline__ void step_epilogue_mail(const StepEpilogue<T> *ep) {
+    if (blockIdx.x != 0u || threadIdx.x != 0u) return;
+    const unsigned *src = ep->mail_src;
+    if (src == nullptr) return;
+    const unsigned long long w = (unsigned long long)__builtin_nontemporal_load(src) | ((unsigned long long)__builtin_nontemporal_load(src + 1) << 32);
+    __threadfence_system();
+    *reinterpret_cast<volatile unsigned long long *>(ep->mail_dst) = w;
+}
 
 // `comp` (0..3) is the component this lane holds in `tot` (wave_sum4's lanes 0 / 16 / 32 / 48); `own` = x, y, z or w of the row's
 // own position.  standin_gate.h nve_advance + wrap1 and brick.hip shifted(), one component at a time: the same bits.

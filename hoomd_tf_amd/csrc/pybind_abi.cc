@@ -154,6 +154,11 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
     X(htfs_brick_pack_halo_peer) \
     X(htfs_brick_unpack_halo)
 
+// include/htf_step_check.h: the check step without a check launch (_lib.STEP_CHECK_PROTOTYPES)
+#define HTF_STEP_CHECK_FUNCTIONS(X) \
+    X(htfs_nve_step_check) \
+    X(htfs_rebuild_nlist_gated)
+
 // include/htf_cg.h: the coarse-grained ops (_lib.CG_PROTOTYPES)
 #define HTF_CG_FUNCTIONS(X) \
     X(htf_cg_com_forward) \
@@ -190,6 +195,7 @@ PYBIND11_MODULE(_htf_abi, m) {
     m.attr("abi_version") = HTF_AMD_ABI_VERSION;
 #define X(fn) bind(m, #fn, &fn);
     HTF_ABI_FUNCTIONS(X)
+    HTF_STEP_CHECK_FUNCTIONS(X)
     HTF_CG_FUNCTIONS(X)
     HTF_GEOM_FUNCTIONS(X)
     HTF_NLIST_FUNCTIONS(X)

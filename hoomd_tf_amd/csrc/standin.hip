@@ -25,23 +25,8 @@ __global__ __launch_bounds__(256) void nve_step_kernel(typename Vec4<T>::type *_
     vel[i] = v;
 }
 
-// the largest squared displacement of a workgroup's (up to 1024) rows, in its thread 0 (s_max: 16 floats of LDS; ends behind a
-// barrier): the body max_disp_kernel and check_disp_kernel share, so that every form of the check decides on the same bits
-template <typename T>
-__device__ __forceinline__ float block_max_disp2(const typename Vec4<T>::type *__restrict__ pos,
-                                                 const typename Vec4<T>::type *__restrict__ ref, unsigned N, const SBox<T> &b,
-                                                 float *s_max) {
-    unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-    float d2 = 0.f;
-    if (i < N) {
-        auto p = pos[i];
-        auto r = ref[i];
-        T dx = mimg<T>(p.x - r.x, b.L[0], b.Linv[0], b.periodic[0]);
-        T dy = mimg<T>(p.y - r.y, b.L[1], b.Linv[1], b.periodic[1]);
-        T dz = mimg<T>(p.z - r.z, b.L[2], b.Linv[2], b.periodic[2]);
-        d2 = (float)(dx * dx + dy * dy + dz * dz);
-        if (!(d2 == d2)) d2 = 0.f; // an inert row (standin_gate.h) has not moved
-    }
+// the largest of a workgroup's (up to 1024) per-thread values, in its thread 0 (s_max: 16 floats of LDS; ends behind a barrier)
+__device__ __forceinline__ float block_max(float d2, float *s_max) {
     for (int m = 1; m < 64; m <<= 1) d2 = fmaxf(d2, __shfl_xor(d2, m));
     if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = d2;
     __syncthreads();
@@ -50,6 +35,33 @@ __device__ __forceinline__ float block_max_disp2(const typename Vec4<T>::type *_
         for (int m = 1; m < 16; m <<= 1) d2 = fmaxf(d2, __shfl_xor(d2, m));
     }
     return d2;
+}
+
+// the largest squared displacement of a workgroup's rows, in its thread 0: the body max_disp_kernel and check_disp_kernel share
+// (the per-row expression is standin_gate.h row_disp2, nve_check_kernel's too), so that every form of the check decides on the
+// same bits
+template <typename T>
+__device__ __forceinline__ float block_max_disp2(const typename Vec4<T>::type *__restrict__ pos,
+                                                 const typename Vec4<T>::type *__restrict__ ref, unsigned N, const SBox<T> &b,
+                                                 float *s_max) {
+    unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    float d2 = 0.f;
+    if (i < N) d2 = row_disp2<T>(pos[i], ref[i], b);
+    return block_max(d2, s_max);
+}
+
+// A workgroup's maximum (its thread 0's d2 >= 0: uint order == float order) into work[0], then its ticket in work[1]: true, for the
+// whole workgroup, in the LAST one to finish -- every other workgroup's maximum is in.  s_last: one word of LDS.
+__device__ __forceinline__ bool ticket_is_last(float d2, unsigned *__restrict__ work, unsigned *s_last) {
+    if (threadIdx.x == 0) {
+        unsigned last = 0u;
+        if (__float_as_uint(d2) > *(volatile unsigned *)work) atomicMax(work, __float_as_uint(d2));
+        __threadfence();
+        if (atomicAdd(work + 1, 1u) == gridDim.x - 1u) last = 1u;
+        *s_last = last;
+    }
+    __syncthreads();
+    return *s_last != 0u;
 }
 
 template <typename T>
@@ -81,15 +93,8 @@ __global__ __launch_bounds__(1024) void check_disp_kernel(const typename Vec4<T>
                                                           float *__restrict__ h_out, htfs_mirror mirror) {
     __shared__ float s_max[16];
     __shared__ unsigned s_last;
-    if (threadIdx.x == 0) s_last = 0u;
     const float d2 = block_max_disp2<T>(pos, ref, N, b, s_max);
-    if (threadIdx.x == 0) {
-        if (__float_as_uint(d2) > *(volatile unsigned *)work) atomicMax(work, __float_as_uint(d2));
-        __threadfence();
-        if (atomicAdd(work + 1, 1u) == gridDim.x - 1u) s_last = 1u; // every other block's maximum is in
-    }
-    __syncthreads();
-    if (s_last == 0u) return;
+    if (!ticket_is_last(d2, work, &s_last)) return;
     if (CYCLE) {
         for (unsigned m = 0; m < mirror.n; ++m) {
             const unsigned *src = (const unsigned *)mirror.src[m];
@@ -114,6 +119,39 @@ __global__ __launch_bounds__(1024) void check_disp_kernel(const typename Vec4<T>
                 *(volatile unsigned *)(h_out + 1) = cycle;
             }
         }
+    }
+}
+
+// The integrator of the step BEFORE a check that also fills the check's displacement word (htfs_nve_step_check): nve_step_kernel's
+// body -- the same nve_advance, the same stores -- and, on the new position while it is still in registers, check_disp_kernel<T,
+// false>'s reduction: row_disp2 against ref on the LIST's box `lb`, the workgroup's maximum into work[0], a ticket in work[1], the
+// last workgroup publishes *out and leaves both work words zero.  The check step then needs no sweep of its own over the positions
+// the integrator has just written.  1024 threads as the check kernel: one same-address atomic pair per 1024 rows.
+// (the new position goes through an empty asm: what is stored and what is measured is the one rounded value nve_step_kernel
+//  stores, whatever the back end would like to fuse across the two uses)
+template <typename T>
+__global__ __launch_bounds__(1024) void nve_check_kernel(typename Vec4<T>::type *__restrict__ pos, typename Vec4<T>::type *__restrict__ vel,
+                                                         const typename Vec4<T>::type *__restrict__ force,
+                                                         const typename Vec4<T>::type *__restrict__ ref, unsigned N, T dt, SBox<T> b,
+                                                         SBox<T> lb, unsigned *__restrict__ work, float *__restrict__ out) {
+    __shared__ float s_max[16];
+    __shared__ unsigned s_last;
+    unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    float d2 = 0.f;
+    if (i < N) {
+        auto p = pos[i];
+        auto v = vel[i];
+        nve_advance<T>(p, v, force[i], dt, b);
+        asm volatile("" : "+v"(p.x), "+v"(p.y), "+v"(p.z));
+        pos[i] = p;
+        vel[i] = v;
+        d2 = row_disp2<T>(p, ref[i], lb);
+    }
+    d2 = block_max(d2, s_max);
+    if (!ticket_is_last(d2, work, &s_last)) return;
+    if (threadIdx.x == 0) {
+        out[0] = __uint_as_float(atomicExch(work, 0u));
+        work[1] = 0u;
     }
 }
 
@@ -475,6 +513,26 @@ extern "C" int htfs_nve_step(void *d_pos, void *d_vel, const void *d_force, int 
     else
         hipLaunchKernelGGL((nve_step_kernel<double>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (double4 *)d_pos, (double4 *)d_vel, (const double4 *)d_force, N, dt, make_sbox<double>(box));
     return check_launch("nve_step_kernel");
+}
+
+// htfs_nve_step and the distance check of the step behind it in one launch (nve_check_kernel): *d_disp2 <- the word
+// htfs_max_displacement2 would find on the positions this call stores, measured from nl->ref on nl->box, accumulated in the work
+// words of nl->scratch (zero before, zero after: htfs_nlist's promise).  htfs_rebuild_nlist_gated is the rest of the check step.
+extern "C" int htfs_nve_step_check(void *d_pos, void *d_vel, const void *d_force, int dtype, unsigned N, double dt, const htf_box *box,
+                                   const htfs_nlist *nl, float *d_disp2, htf_stream stream) {
+    HTF_REQUIRE(d_pos && d_vel && d_force && box && nl && d_disp2, "htfs_nve_step_check: null pointer");
+    HTF_REQUIRE(nl->ref && nl->scratch, "htfs_nve_step_check: the list has no reference positions or no scratch");
+    HTF_REQUIRE(dtype == HTF_F32 || dtype == HTF_F64, "htfs_nve_step_check: bad dtype %d", dtype);
+    if (N == 0) return HTF_OK;
+    const unsigned ncell = (unsigned)(nl->ncell3[0] * nl->ncell3[1] * nl->ncell3[2]);
+    HTF_REQUIRE(ncell > 0, "htfs_nve_step_check: no cells");
+    unsigned *work = nl->scratch + HTFS_SCRATCH_WORK(ncell);
+    const unsigned grid = (N + 1023) / 1024;
+    if (dtype == HTF_F32)
+        hipLaunchKernelGGL((nve_check_kernel<float>), dim3(grid), dim3(1024), 0, (hipStream_t)stream, (float4 *)d_pos, (float4 *)d_vel, (const float4 *)d_force, (const float4 *)nl->ref, N, (float)dt, make_sbox<float>(box), make_sbox<float>(&nl->box), work, d_disp2);
+    else
+        hipLaunchKernelGGL((nve_check_kernel<double>), dim3(grid), dim3(1024), 0, (hipStream_t)stream, (double4 *)d_pos, (double4 *)d_vel, (const double4 *)d_force, (const double4 *)nl->ref, N, dt, make_sbox<double>(box), make_sbox<double>(&nl->box), work, d_disp2);
+    return check_launch("nve_check_kernel");
 }
 
 extern "C" int htfs_max_displacement2(const void *d_pos, const void *d_ref, int dtype, unsigned N, const htf_box *box,
@@ -1026,6 +1084,20 @@ extern "C" int htfs_rebuild_nlist(const htfs_nlist *nl, const void *d_pos, int d
     return rebuild_nlist_impl(nl, d_pos, dtype, N, Ntot, scratch_clean != 0, stream, htf::kOpenGate);
 }
 
+// what a check step does behind its displacement word: the rebuild with every kernel gated on the word, the two status words
+// standing in for the list's max_neigh and counter, and (h_stat2 nullable) their copy to pinned host memory
+static int gated_rebuild(const htfs_nlist *nl, const void *d_pos, int dtype, unsigned N, unsigned Ntot, bool scratch_clean, float *d_disp2,
+                         double threshold2, unsigned *d_stat2, unsigned *h_stat2, htf_stream stream) {
+    htfs_nlist l = *nl;
+    l.max_neigh = d_stat2;
+    l.counter = d_stat2 + 1;
+    int rc = rebuild_nlist_impl(&l, d_pos, dtype, N, Ntot, scratch_clean, stream, htf::Gate{d_disp2, (float)threshold2});
+    if (rc != HTF_OK) return rc;
+    if (h_stat2 != nullptr)
+        HTF_CHECK_HIP(hipMemcpyAsync(h_stat2, d_stat2, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    return HTF_OK;
+}
+
 // A whole check step of a device-decided list in ONE call (the host's share of a small system's step is its enqueue), SEVEN stream
 // operations, five of them gated: the displacement word filled by ONE launch (check_disp_kernel<T, false>: the blocks accumulate
 // into the scratch's two work words, the last one -- by ticket -- publishes *d_disp2 and leaves the work words zero, where a memset
@@ -1052,12 +1124,17 @@ extern "C" int htfs_check_rebuild_nlist(const htfs_nlist *nl, const void *d_pos,
         hipLaunchKernelGGL((check_disp_kernel<double, false>), dim3(grid), dim3(1024), 0, s, (const double4 *)d_pos, (const double4 *)nl->ref, N, make_sbox<double>(&nl->box), work, d_disp2, (float *)nullptr, none);
     int rc = check_launch("check_disp_kernel");
     if (rc != HTF_OK) return rc;
-    htfs_nlist l = *nl;
-    l.max_neigh = d_stat2;
-    l.counter = d_stat2 + 1;
-    rc = rebuild_nlist_impl(&l, d_pos, dtype, N, Ntot, true, stream, Gate{d_disp2, (float)threshold2});
-    if (rc != HTF_OK) return rc;
-    if (h_stat2 != nullptr)
-        HTF_CHECK_HIP(hipMemcpyAsync(h_stat2, d_stat2, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    return HTF_OK;
+    return gated_rebuild(nl, d_pos, dtype, N, Ntot, true, d_disp2, threshold2, d_stat2, h_stat2, stream);
+}
+
+// The same check step when the displacement word is already there (htfs_nve_step_check filled it in the integrator's launch): the
+// five gated launches and, unless the caller has the status words delivered another way (h_stat2_by_mail: the step epilogue of the
+// force launch behind this call, htfs_step_epilogue's mail), their copy.  No check launch.
+extern "C" int htfs_rebuild_nlist_gated(const htfs_nlist *nl, const void *d_pos, int dtype, unsigned N, unsigned Ntot, int scratch_clean,
+                                        float *d_disp2, double threshold2, unsigned *d_stat2, unsigned *h_stat2, int h_stat2_by_mail,
+                                        htf_stream stream) {
+    HTF_REQUIRE(nl && nl->ref && nl->scratch && d_pos && d_disp2 && d_stat2, "htfs_rebuild_nlist_gated: null pointer");
+    if (N == 0) return HTF_OK;
+    return gated_rebuild(nl, d_pos, dtype, N, Ntot, scratch_clean != 0, d_disp2, threshold2, d_stat2, h_stat2_by_mail ? nullptr : h_stat2,
+                         stream);
 }

@@ -54,6 +54,19 @@ __device__ __forceinline__ T mimg(T d, T L, T Linv, int periodic) {
     return periodic ? d - L * rint(d * Linv) : d;
 }
 
+// the squared displacement of one row from its reference position, as the distance check measures it: the minimum image per axis,
+// the sum in this order, the cast to float, 0 for an inert row (it has not moved).  Written once, for every kernel that fills the
+// displacement word (max_disp_kernel, check_disp_kernel, nve_check_kernel), so that every form of the check decides on the same bits
+template <typename T, typename V4>
+__device__ __forceinline__ float row_disp2(const V4 &p, const V4 &r, const SBox<T> &b) {
+    T dx = mimg<T>(p.x - r.x, b.L[0], b.Linv[0], b.periodic[0]);
+    T dy = mimg<T>(p.y - r.y, b.L[1], b.Linv[1], b.periodic[1]);
+    T dz = mimg<T>(p.z - r.z, b.L[2], b.Linv[2], b.periodic[2]);
+    float d2 = (float)(dx * dx + dy * dy + dz * dz);
+    if (!(d2 == d2)) d2 = 0.f; // an inert row has not moved
+    return d2;
+}
+
 // the leapfrog update of one particle (IntegratorTwoStep + TwoStepNVE analogue, unit mass): shared by nve_step_kernel and the
 // brick decomposition's integrate-and-pack kernel so that both produce the same bits
 template <typename T, typename V4>

@@ -562,16 +562,22 @@ class Context:
         domain.exchange_end()
         self.compute_forces(timestep, arrays, stream, rows=(n_int, arrays.N - n_int))
 
-    def set_step_epilogue(self, slot, vel, pos_next, dt, box, brick=None, row_slots=None, halo_send=None, ghost_direct=None):
+    def set_step_epilogue(self, slot, vel, pos_next, dt, box, brick=None, row_slots=None, halo_send=None, ghost_direct=None, mail=None):
         """Register a step epilogue (include/htf_standin.h htfs_step_epilogue: the stand-in integrator, and a brick's halo pack, done
         by the force kernel's own lanes) in descriptor ``slot`` (0 / 1: the two directions of a position ping-pong) -> whether this
-        context's launches will honour it.  A blocking upload: set-up time."""
+        context's launches will honour it.  A blocking upload: set-up time.  ``mail``: (two int32 words on the device, two in PINNED host
+        memory) that a launch selected with ``use_step_epilogue(slot, mail=True)`` carries from the one to the other."""
         e = _lib.StepEpilogue()
         e.d_vel, e.d_pos_next = _dev(vel, "vel", self.scalar_dtype).data_ptr(), _dev(pos_next, "pos_next", self.scalar_dtype).data_ptr()
         e.dtype, e.dt = self.cfg.scalar_dtype, float(dt)
         e.box = box
         self._epilogue_keep = getattr(self, "_epilogue_keep", {})
-        self._epilogue_keep[slot] = (vel, pos_next, brick, row_slots, halo_send, ghost_direct)
+        self._epilogue_keep[slot] = (vel, pos_next, brick, row_slots, halo_send, ghost_direct, mail)
+        if mail is not None:
+            src, dst = mail
+            if not (src.is_cuda and dst.is_pinned() and src.numel() >= 2 and dst.numel() >= 2 and src.element_size() == 4 == dst.element_size()):
+                raise ValueError("set_step_epilogue: mail is (two 32-bit words on the device, two in pinned host memory)")
+            e.d_mail_src, e.h_mail_dst = src.data_ptr(), dst.data_ptr()
         if brick is not None:
             e.brick = C.addressof(brick)
             e.d_row_slots = row_slots.data_ptr()
@@ -581,9 +587,10 @@ class Context:
         check(lib.htfs_set_step_epilogue(self._h, int(slot), C.byref(e), C.byref(ok)))
         return bool(ok.value)
 
-    def use_step_epilogue(self, slot):
-        """The descriptor every later compute_forces of this context carries (-1 / None: none)."""
-        check(lib.htfs_use_step_epilogue(self._h, -1 if slot is None else int(slot)))
+    def use_step_epilogue(self, slot, mail=False):
+        """The descriptor every later compute_forces of this context carries (-1 / None: none); ``mail``: the one that also delivers
+        the mail the slot was registered with."""
+        check(lib.htfs_use_step_epilogue(self._h, -1 if slot is None else int(slot), int(bool(mail))))
 
     def profile_enable(self, on=True):
         """Event-bracket the build and eval scopes (HOOMD Profiler analogue); ``on=k`` (int > 1)

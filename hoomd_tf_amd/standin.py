@@ -201,6 +201,10 @@ class CellNlist:
         self._stat = self._stat_host = self._stat_event = None
         self._max_host = self._max_event = None
         self._mirrored = False      # BrickRun: the check kernel of a captured cycle carries _max to _max_host
+        # the displacement word of the NEXT check, left in _disp by the integrator's launch of the step before it (FusedStep,
+        # htfs_nve_step_check): (timestep, by_mail, what it was measured on and against); see arm_step_check
+        self._armed = None
+        self._mail_pending = None   # the check step whose status words the force launch behind it was left to deliver
 
     def subscribe(self, rcut_fn):
         """NeighborList r_cut subscription (tensorflowcompute.py:116-120): the list is
@@ -271,6 +275,7 @@ class CellNlist:
 
     def build(self):
         s = self.sys
+        self._armed = None   # (a word measured from the old reference positions dies with them)
         if self.domain is not None:
             self.domain.rebuild()  # Communicator: migrate particles, re-plan + fill ghosts
         Ntot = self._size_grid()
@@ -354,16 +359,22 @@ class CellNlist:
         else:
             self._ref.copy_(s.pos[: s.N])
 
-    def _enqueue_rebuild(self, Ntot, gated):
+    def _enqueue_rebuild(self, Ntot, gated, word_by_mail=None):
         """The one route to a rebuild after the first: ONE C call on the descriptor.  ``gated``: behind the distance check,
-        decided on the device, status words to pinned memory (htf_standin.h htfs_check_rebuild_nlist); else unconditional."""
+        decided on the device, status words to pinned memory (htf_standin.h htfs_check_rebuild_nlist); else unconditional.
+        ``word_by_mail`` (not None: the displacement word is already in ``_disp``, arm_step_check): the gated launches alone
+        (htfs_rebuild_nlist_gated), and when it is True no copy of the status words either -- the next force launch carries them."""
         s, d = self.sys, self._desc
         # the binning scratch is this object's own and every completed binning leaves its counts zero (its last small kernel): no memset
         key = (d.scratch, self._grid[2])
         clean = int(self._scratch_clean == key)
         self._scratch_clean = None   # (a call that fails half way leaves the counts dirty: the next one zeroes them again)
         stream = C.c_void_p(raw_stream(s.device.index))
-        if gated:
+        if gated and word_by_mail is not None:
+            check(lib.htfs_rebuild_nlist_gated(C.byref(d), s.pos.data_ptr(), s.scalar_code, s.N, Ntot, clean, self._disp.data_ptr(),
+                                               (self.r_buff / 2.0) ** 2, self._stat.data_ptr(), self._stat_host.data_ptr(),
+                                               int(word_by_mail), stream))
+        elif gated:
             check(lib.htfs_check_rebuild_nlist(C.byref(d), s.pos.data_ptr(), s.scalar_code, s.N, Ntot, clean, self._disp.data_ptr(),
                                                (self.r_buff / 2.0) ** 2, self._stat.data_ptr(), self._stat_host.data_ptr(), stream))
         else:
@@ -423,16 +434,62 @@ class CellNlist:
                 and (self.domain is None or self.domain.world == 1) and self.sys.n_ghost == 0
                 and self._ref.shape[0] == self.sys.N and self._scr_n is not None and self._scr_n[0] == self.sys.N)
 
-    def check_and_rebuild_on_device(self):
-        """NeighborList::compute at a check step with the decision left to the device: distance check, then
-        the whole rebuild gated on its result.  No host synchronisation."""
-        if not self._capturing:  # (inside a hipGraph capture: no host-side waits)
-            self._poll_overflow()
+    def _ensure_stat(self):
         if self._stat is None:
             self._stat = torch.zeros(2, dtype=torch.int32, device=self.sys.device)  # [largest row of the last rebuild, rebuilds]
             self._stat_host = torch.zeros(2, dtype=torch.int32).pin_memory()
-        self._enqueue_rebuild(self.sys.N, gated=True)
-        if not self._capturing:
+
+    def _check_state(self):
+        """What a displacement word was measured on and against: the position array and the reference positions (address and
+        torch's version counter: an in-place write bumps it), the scratch whose work words the measuring launch used and left
+        zero, the grid, the build count."""
+        s, d = self.sys, self._desc
+        return (s.pos.data_ptr(), s.pos._version, self._ref.data_ptr(), self._ref._version, d.scratch, self._grid[2], self.n_builds,
+                s.N, self.r_buff)
+
+    def step_check_ready(self):
+        """Whether the integrator's launch may fill the next check's displacement word (FusedStep): a device-decided list whose
+        scratch -- the work words are part of it -- is known clean, outside a capture."""
+        return (self._device_ok() and not self._capturing and self._grid is not None
+                and self._scratch_clean == (self._desc.scratch, self._grid[2]))
+
+    def arm_step_check(self, timestep, by_mail):
+        """The caller's integrator launch has left in ``_disp`` the word the check of ``timestep`` would measure on ``sys.pos``
+        as it is now (htfs_nve_step_check).  That check then enqueues the gated launches alone -- if nothing it depends on has
+        changed by then; anything else (build(), another array, a write into the positions, another timestep) and it measures
+        again.  ``by_mail``: the force launch behind that check will carry the status words to the host (its step epilogue's mail)."""
+        self._ensure_stat()
+        self._armed = (int(timestep), bool(by_mail), self._check_state())
+
+    def _take_armed(self, timestep):
+        """-> None (measure: the full check) or ``by_mail`` of a word armed for exactly this check."""
+        armed, self._armed = self._armed, None
+        if armed is None or self._capturing or timestep is None or armed[0] != int(timestep) or armed[2] != self._check_state():
+            return None
+        return armed[1]
+
+    def take_mail(self, timestep):
+        """Whether the check of ``timestep`` left its status words to the force launch of the same step (asked by that launch's
+        owner, which then calls mark_check_enqueued() behind it)."""
+        pending, self._mail_pending = self._mail_pending, None
+        return pending is not None and pending == timestep
+
+    def check_and_rebuild_on_device(self, timestep=None):
+        """NeighborList::compute at a check step with the decision left to the device: distance check, then
+        the whole rebuild gated on its result.  No host synchronisation.  Where the integrator of the step before has left the
+        check's word behind (arm_step_check for this ``timestep``), the gated rebuild alone."""
+        if not self._capturing:  # (inside a hipGraph capture: no host-side waits)
+            self._poll_overflow()
+        self._ensure_stat()
+        if self._mail_pending is not None:
+            # (a mail nobody took: the force launch it was left to never came.  The words by copy then, one check later)
+            self._mail_pending = None
+            self._stat_host.copy_(self._stat, non_blocking=True)
+        by_mail = self._take_armed(timestep)
+        self._enqueue_rebuild(self.sys.N, gated=True, word_by_mail=by_mail)
+        if by_mail:
+            self._mail_pending = timestep     # (the event goes behind the force launch that delivers: take_mail)
+        elif not self._capturing:
             self.mark_check_enqueued()
 
     def graph_key(self):
@@ -441,7 +498,9 @@ class CellNlist:
         d = self._desc
         return (tuple(getattr(d, name) or 0 for name, ctype in d._fields_ if ctype is C.c_void_p)
                 + tuple(0 if b is None else b.data_ptr() for b in (self._disp, self._stat, self._stat_host))
-                + (int(self.type_split), self.check_period))
+                # (the form of the check: a period recorded behind an armed word -- arm_step_check -- would replay without its check
+                #  launch; a capture never takes that form, _take_armed, so a replay always measures what it finds)
+                + (int(self.type_split), self.check_period, "check measures"))
 
     def device_builds(self):
         """Rebuilds the device has decided on so far (synchronises; for reports, not for the step loop)."""
@@ -526,8 +585,9 @@ class CellNlist:
         self._step_done = timestep
         if self._device_ok():
             if timestep % self.check_period == 0:
-                self.check_and_rebuild_on_device()
+                self.check_and_rebuild_on_device(timestep)
             return
+        self._armed = None   # (the host decides, or a domain, or a sorter: every check measures)
         if self._ref is None or (timestep % self.check_period == 0 and self.needs_update()):
             self.build()
         elif self.domain is not None:
@@ -594,10 +654,15 @@ class FusedStep:
         self._slot_of = {}
         self._arr = {}
         self._arr_key = None
+        self._mail_ok = False        # the epilogue slots were registered with the list's status words as their mail
+        self._check_in_step = False  # the classic step before a check fills the check's displacement word (htfs_nve_step_check)
         self.available = self._register()
 
     def _register(self):
         s, dom, ctx = self.sys, self.dom, self.ctx
+        # HTF_NO_CHECK_IN_STEP=1: every check measures for itself and copies its status words, as before (A/B runs, tests)
+        self._check_in_step = (os.environ.get("HTF_NO_CHECK_IN_STEP") != "1" and dom is None and self.nve.group is None
+                               and s.pos.is_cuda and self.nl.device_decision)
         if os.environ.get("HTF_NO_STEP_EPILOGUE") == "1" or self.nve.group is not None or not s.pos.is_cuda:
             return False
         fixed = dom is not None and getattr(dom, "fixed_capacity", False)
@@ -608,6 +673,9 @@ class FusedStep:
         ok = True
         for slot, (cur, nxt) in enumerate(((s.pos, self._twin), (self._twin, s.pos))):
             kw = {}
+            if self._check_in_step:
+                self.nl._ensure_stat()
+                kw = dict(mail=(self.nl._stat, self.nl._stat_host))
             if fixed:
                 dom.enable_row_slots()
                 direct = dom.transport == "local"
@@ -618,6 +686,7 @@ class FusedStep:
         if not ok:
             self._twin = None
             return False
+        self._mail_ok = self._check_in_step
         self._home = s.pos.data_ptr()    # the array every check period starts and ends on (captured cycles carry it by value)
         if fixed and dom.transport == "local":
             # a rank that is its own neighbor: the epilogue writes the LIVE rows of a message straight into the other array's ghost
@@ -639,18 +708,25 @@ class FusedStep:
         """The force rows of step ``ts`` (interior rows while a posted halo is in flight, boundary rows behind it) and the
         integrator: ONE launch each way, the positions swapped behind it -- except on the last step of a check period that finds
         the positions in their home array (an odd period: four swaps and one classic step), so that every period starts on the
-        same array whatever the period and wherever the run began: a captured period replays from fixed addresses."""
+        same array whatever the period and wherever the run began: a captured period replays from fixed addresses.
+        That classic step, when the next step is a check of a device-decided list, integrates with htfs_nve_step_check: the
+        launch that stores the new positions also leaves the check's displacement word behind (CellNlist.arm_step_check), and
+        the check step's force launch carries the check's status words to the host (the epilogue's mail) -- a check is then the
+        gated launches and nothing else."""
         s, dom, ctx = self.sys, self.dom, self.ctx
         if dom is not None and dom.pending and (not dom.overlaps or 20 * dom.n_interior < s.N):
             dom.exchange_end()          # nothing in flight to hide, or next to no interior rows to hide it behind: one launch
         P = self.nl.check_period
         fused = self.available and not (ts % P == P - 1 and s.pos.data_ptr() == self._home)
         if fused:
-            ctx.use_step_epilogue(self._slot_of[s.pos.data_ptr()])
+            mail = self._mail_ok and self.nl.take_mail(ts)
+            ctx.use_step_epilogue(self._slot_of[s.pos.data_ptr()], mail=mail)
             try:
                 ctx.compute_forces_overlapped(ts, self.arrays(), dom)
             finally:
                 ctx.use_step_epilogue(None)
+            if mail:
+                self.nl.mark_check_enqueued()        # (what the next check waits for: the launch that delivers the words)
             nxt = self._twin
             self._twin, s.pos = s.pos, nxt          # x(t + dt) is in the other array now
             if dom is not None:
@@ -659,6 +735,12 @@ class FusedStep:
         ctx.compute_forces_overlapped(ts, self.arrays(), dom)
         if dom is not None and getattr(dom, "kernels", False) and self.nve.group is None:
             dom.nve_step(self.nve.dt)               # integrator + next step's halo messages, one launch
+        elif self._check_in_step and (ts + 1) % P == 0 and self.nl.step_check_ready():
+            nl = self.nl
+            check(lib.htfs_nve_step_check(s.pos.data_ptr(), s.vel.data_ptr(), s.force.data_ptr(), s.scalar_code, s.N, self.nve.dt,
+                                          C.byref(s.box), C.byref(nl._desc), nl._disp.data_ptr(), C.c_void_p(raw_stream(s.device.index))))
+            # (by mail where step ts + 1 is a one-launch step: every period but a period of one step)
+            nl.arm_step_check(ts + 1, by_mail=self._mail_ok and self.available and P > 1)
         else:
             self.nve.step()
 

@@ -280,9 +280,17 @@ typedef struct htfs_step_epilogue {
     const unsigned *d_row_slots; /* [cap_bnd][HTFS_BRICK_MAX_MSG]: htfs_brick_row_slots */
     void *d_halo_send;           /* [sum ghost_cap] Scalar4 (a transport sends it), or NULL */
     void *d_ghost_direct;        /* the ghost region of d_pos_next (this rank is its own neighbor), or NULL */
+    /* the MAIL of a launch (both NULL: none): two status words an earlier launch on the stream left on the device -- a
+     * device-decided list's [largest row, rebuilds] -- that one lane of the force launch carries to pinned host memory (8-byte
+     * aligned; one 8-byte store behind a system-scope fence: never torn) while the rows are evaluated, where a copy behind the
+     * rebuild chain was a stream operation of its own.  A slot registered with mail holds a second descriptor that carries it;
+     * htfs_use_step_epilogue's `mail` selects that one, for the force launch of a check step */
+    const unsigned *d_mail_src;
+    unsigned *h_mail_dst;
 } htfs_step_epilogue;
 HTF_API int htfs_set_step_epilogue(htf_ctx *ctx, int slot, const htfs_step_epilogue *ep, int *applies);
-HTF_API int htfs_use_step_epilogue(htf_ctx *ctx, int slot);
+/* slot -1: none.  mail != 0: the slot's descriptor with the mail (an error when the slot was registered without) */
+HTF_API int htfs_use_step_epilogue(htf_ctx *ctx, int slot, int mail);
 /* d_row_slots[j][m] <- the slot of boundary row j in halo message m, 0xFFFFFFFF where the row is not in it (or beyond the message's
  * count): the class boundaries and slot table of the last re-plan, once per re-plan instead of once per row and step. */
 HTF_API int htfs_brick_row_slots(const htfs_brick *g, const unsigned *d_counts, unsigned *d_row_slots, htf_stream stream);
@@ -334,4 +342,6 @@ HTF_API int htfs_mailbox_allreduce_max_f32(const htfs_reduce_box *rb, float *d_v
 #ifdef __cplusplus
 }
 #endif
+/* the check step without a check launch (htfs_nve_step_check, htfs_rebuild_nlist_gated): part of this interface, in a file of its own */
+#include "htf_step_check.h"
 #endif

@@ -58,7 +58,9 @@ __host__ __device__ inline int desc_lds_weights(int D, int H1, int H2) { return 
 
 // FORCES = false: G alone, written to out [B][D].  FORCES = true: out [B][4] (f, E) and, with VIRIAL, virial9 [B][9].
 // n work items: rows 0 .. n - 1, or rows[0 .. n - 1] with LIST (rows is then not null).
-template <bool FORCES, bool TANH, bool VIRIAL, bool CUT, bool LIST, typename IT>
+// GRAD (with FORCES, pass 1 of the conservative forces, cforce.hip): the row ends after step 4 -- out [B][D] fp32 receives
+// g = dE/dG from lanes < D and virial9 [B] fp32 the energy, the bits the force instantiation writes.
+template <bool FORCES, bool TANH, bool VIRIAL, bool CUT, bool LIST, typename IT, bool GRAD = false>
 __device__ __forceinline__ void desc_rows(const typename Vec4<IT>::type *__restrict__ nlist, const int *__restrict__ rows, unsigned n,
                                           unsigned NN, const float *__restrict__ weights, const float *__restrict__ mu, int K, int T,
                                           int H1, int H2, float gap, float rc, void *__restrict__ out, int out_f64,
@@ -195,6 +197,11 @@ __device__ __forceinline__ void desc_rows(const typename Vec4<IT>::type *__restr
         float gG = 0.f;
         if ((int)lane < D) {
             for (int a = 0; a < H1; ++a) gG = fmaf(s_x[a], W1[lane * ld1 + a], gG);
+        }
+        if constexpr (GRAD) {
+            if ((int)lane < D) ((float *)out)[(size_t)row * D + lane] = gG;
+            if (lane == 0) ((float *)virial9)[row] = energy;
+            continue;
         }
         line_publish(s_x, lane, gG);
 

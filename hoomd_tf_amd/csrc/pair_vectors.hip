@@ -308,3 +308,103 @@ extern "C" int htf_build_pair_vectors(void *dest, int dest_dtype, const void *d_
     return htf::build_pair_vectors_impl(dest, dest_dtype, d_pos, pos_dtype, N, NN, offset, batch_size, box, d_n_neigh,
                                         d_nlist, d_head_list, rmax, d_max_count, nullptr, nullptr, (hipStream_t)stream);
 }
+
+// ---- the slot-aligned index tensor (include/htf_cforce.h): which particle sits in each slot of the tensor above ----
+// One wave per row, build_row's two sweeps with the particle index stored where build_row stores the pair vector: the same
+// min_image, the same keep predicate, the same ballot ranks, hence the same slots -- overflowing rows included (entry q in
+// slot q % NN, survivors replayed in order after the first sweep's stores have retired).  Empty slots hold -1.
+#include "htf_cforce.h"
+
+namespace htf {
+
+template <typename PT, bool REPLAY>
+__device__ __forceinline__ unsigned index_sweep(int *__restrict__ row, const typename Vec4<PT>::type *__restrict__ pos,
+                                                const unsigned *__restrict__ nl, unsigned nn, const typename Vec4<PT>::type pi,
+                                                const BoxT<PT> &box, PT rmaxsq, unsigned NN, unsigned lane, unsigned lo) {
+    using PV = typename Vec4<PT>::type;
+    unsigned Q = 0;
+    for (unsigned base = 0; base < nn; base += 64 * kChunk) {
+        unsigned k[kChunk];
+        PV pk[kChunk];
+#pragma unroll
+        for (int t = 0; t < kChunk; ++t) {
+            unsigned j = base + t * 64 + lane;
+            k[t] = nl[j < nn ? j : nn - 1];
+        }
+#pragma unroll
+        for (int t = 0; t < kChunk; ++t) pk[t] = pos[k[t]];
+#pragma unroll
+        for (int t = 0; t < kChunk; ++t) {
+            if (base + t * 64 >= nn) break; // wave-uniform
+            unsigned j = base + t * 64 + lane;
+            PT dx = pk[t].x - pi.x, dy = pk[t].y - pi.y, dz = pk[t].z - pi.z;
+            min_image<PT>(dx, dy, dz, box);
+            PT rsq = dx * dx + dy * dy + dz * dz;
+            bool keep = (j < nn) && !(rsq > rmaxsq);
+            unsigned long long m = __ballot(keep);
+            unsigned q = Q + ballot_rank(m);
+            Q += __popcll(m);
+            if constexpr (!REPLAY) {
+                if (keep && q < NN) row[q] = (int)k[t];
+            } else {
+                if (keep && q >= lo) row[q % NN] = (int)k[t];
+            }
+        }
+    }
+    return Q;
+}
+
+template <typename PT>
+__global__ __launch_bounds__(256) void cf_pair_kernel(int *__restrict__ dest, const typename Vec4<PT>::type *__restrict__ pos,
+                                                      unsigned NN, unsigned offset, unsigned batch, BoxT<PT> box,
+                                                      const unsigned *__restrict__ n_neigh, const unsigned *__restrict__ nlist,
+                                                      const unsigned *__restrict__ head_list, PT rmaxsq) {
+    const unsigned lane = threadIdx.x & 63u;
+    const unsigned w = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    if (w >= batch) return;
+    const unsigned idx = w + offset;
+    const unsigned nn = n_neigh[idx];
+    const unsigned *nl = nlist + head_list[idx];
+    const auto pi = pos[idx];
+    int *row = dest + (size_t)w * NN;
+    const unsigned Q = nn ? index_sweep<PT, false>(row, pos, nl, nn, pi, box, rmaxsq, NN, lane, 0u) : 0u;
+    for (unsigned s = (Q < NN ? Q : NN) + lane; s < NN; s += 64) row[s] = -1;
+    if (Q > NN) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned lo = Q - NN > NN ? Q - NN : NN;
+        index_sweep<PT, true>(row, pos, nl, nn, pi, box, rmaxsq, NN, lane, lo);
+    }
+}
+
+template <typename PT>
+static int launch_pair_index(int *dest, const void *pos, unsigned NN, unsigned offset, unsigned batch, const htf_box *hb,
+                             const unsigned *n_neigh, const unsigned *nlist, const unsigned *head_list, double rmax,
+                             hipStream_t stream) {
+    BoxT<PT> b = make_boxt<PT>(hb);
+    PT rc = (PT)rmax;
+    PT rmaxsq = rc * rc;
+    hipLaunchKernelGGL((cf_pair_kernel<PT>), dim3((batch + 3) / 4), dim3(256), 0, stream, dest, (const typename Vec4<PT>::type *)pos, NN,
+                       offset, batch, b, n_neigh, nlist, head_list, rmaxsq);
+    return check_launch("cf_pair_kernel");
+}
+
+} // namespace htf
+
+extern "C" int htf_cf_pair_index(int *d_index, const void *d_pos, int pos_dtype, unsigned N, unsigned NN, unsigned offset,
+                                 unsigned batch_size, const htf_box *box, const unsigned *d_n_neigh, const unsigned *d_nlist,
+                                 const unsigned *d_head_list, double rmax, htf_stream stream) {
+    using namespace htf;
+    HTF_REQUIRE(d_index && d_pos && d_n_neigh && d_nlist && d_head_list && box, "htf_cf_pair_index: null pointer");
+    HTF_REQUIRE(NN > 0, "htf_cf_pair_index: NN must be > 0");
+    HTF_REQUIRE(offset <= N && batch_size <= N - offset, "htf_cf_pair_index: batch [%u, %u) exceeds N=%u", offset, offset + batch_size, N);
+    HTF_REQUIRE(rmax > 0, "htf_cf_pair_index: rmax must be > 0");
+    for (int d = 0; d < 3; ++d)
+        HTF_REQUIRE(box->hi[d] > box->lo[d], "htf_cf_pair_index: empty box along %d", d);
+    HTF_REQUIRE(pos_dtype == HTF_F32 || pos_dtype == HTF_F64, "htf_cf_pair_index: bad dtype %d", pos_dtype);
+    if (batch_size == 0) return HTF_OK;
+    if (pos_dtype == HTF_F32)
+        return launch_pair_index<float>(d_index, d_pos, NN, offset, batch_size, box, d_n_neigh, d_nlist, d_head_list, rmax,
+                                        (hipStream_t)stream);
+    return launch_pair_index<double>(d_index, d_pos, NN, offset, batch_size, box, d_n_neigh, d_nlist, d_head_list, rmax,
+                                     (hipStream_t)stream);
+}

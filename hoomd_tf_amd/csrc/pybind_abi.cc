@@ -18,6 +18,7 @@
 #include "htf_geom.h"
 #include "htf_nlist.h"
 #include "htf_bp.h"
+#include "htf_cforce.h"
 
 namespace py = pybind11;
 
@@ -185,6 +186,12 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
     X(htf_bp_scratch_floats) \
     X(htf_bp_loss_grad)
 
+// include/htf_cforce.h: the conservative forces of the descriptor network (_lib.CF_PROTOTYPES)
+#define HTF_CF_FUNCTIONS(X) \
+    X(htf_cf_grad) \
+    X(htf_cf_forces) \
+    X(htf_cf_pair_index)
+
 PYBIND11_MODULE(_htf_abi, m) {
     m.doc() = "pybind11 binding of libhtf_amd.so's C ABI: pointers as integers";
     // a stale module (or library): this module's templates were instantiated from one header, the library it resolved at load
@@ -200,5 +207,6 @@ PYBIND11_MODULE(_htf_abi, m) {
     HTF_GEOM_FUNCTIONS(X)
     HTF_NLIST_FUNCTIONS(X)
     HTF_BP_FUNCTIONS(X)
+    HTF_CF_FUNCTIONS(X)
 #undef X
 }

@@ -323,6 +323,18 @@ class DescriptorMLP:
     the device.  ``loss_gradient`` is also the offline entry: with ``iter_from_trajectory`` and ``ops.optimizer_step`` on
     ``w`` it trains from stored frames.  The centres and their spacing are not trained.  With the default
     ``trainable=False`` a training run raises.
+
+    ``conservative=True`` makes ``compute_nlist_forces`` return the forces of the total energy, ``F = -d(sum_i E_i)/dr``
+    (``total_forces``, include/htf_cforce.h), instead of the row operator's ``2 sum_j dE_i/dx_ij``: ``E_j`` also depends on
+    ``r_i`` through ``G_j``, and two sweeps add that term -- the first writes ``g_i = dE_i/dG_i`` for every row, the second
+    gathers ``g_j`` for every slot.  They conserve momentum and ``KE + sum_i E_i``.  The second sweep needs the particle in
+    each slot: ``htf.Nlist(tensor, index)``, which ``tfcompute`` provides for the step's own list; offline,
+    ``compute_nlist(..., sorted=True, return_types=False)[:, :, 3]`` is the index that goes with the ``return_types=True``
+    tensor (both calls produce the same slots).  With ``n_types > 1`` it also needs the rows' own types:
+    ``layer(nlist, positions)``.  The forces are exact when the list is symmetric within the descriptor's range -- full
+    lists, no overflow, ``r_cut`` not above the list's cutoff -- which is not checked.  Energies are the row operator's, bit
+    for bit.  Not with ``trainable=True`` (the sweep differentiates the row operator), batches, domain decomposition or a
+    mapped list: each raises.
     Limits: ``n_types * K <= 64``, ``H1, H2 <= 64``, at most 256 neighbor slots."""
 
     name = 'descriptor-mlp'
@@ -332,9 +344,12 @@ class DescriptorMLP:
     l1_reg = (0.0,)
 
     def __init__(self, K=16, H1=32, H2=32, low=0.0, high=3.0, n_types=1, activation="tanh", seed=3, device=None,
-                 trainable=False, r_cut=None, n_species=1):
+                 trainable=False, r_cut=None, n_species=1, conservative=False):
         K, H1, H2, n_types, n_species = int(K), int(H1), int(H2), int(n_types), int(n_species)
-        self.trainable = bool(trainable)
+        self.trainable, self.conservative = bool(trainable), bool(conservative)
+        if self.trainable and self.conservative:
+            raise ValueError("DescriptorMLP: conservative=True cannot be trainable: the force-matching sweep differentiates "
+                             "the row operator's forces")
         if r_cut is not None:
             r_cut = float(np.float32(r_cut))
             if not (np.isfinite(r_cut) and r_cut > 0):
@@ -374,6 +389,8 @@ class DescriptorMLP:
             cfg['r_cut'] = self.r_cut
         if self.n_species != 1:
             cfg['n_species'] = self.n_species
+        if self.conservative:
+            cfg['conservative'] = True
         return cfg
 
     def get_weights(self):
@@ -477,6 +494,48 @@ class DescriptorMLP:
                                     ops._stream(x)))
         return (out, v) if virial else out
 
+    def total_forces(self, x, index, virial=False, types=None, species=None):
+        """The forces of the total energy, ``F = -d(sum_i E_i)/dr`` (include/htf_cforce.h), on a pair-vector tensor ``x``
+        [B, NN, 4] (fp32 or fp64): [B, 4] in ``x``'s dtype with ``E_i`` (``forces``' bits) in column 3, and with ``virial``
+        the [B, 3, 3] ``W_i = -1/2 sum_s x_ij (outer) phi_is``.  ``index`` [B, NN]: the particle in each slot, int32 or a float
+        tensor taken by ``rint``; a value outside ``[0, B)`` leaves that slot without its reverse term.  ``types``: the rows'
+        own types, [B] or [B, 4] (column 3), required when ``n_types > 1``.  ``species`` as for ``forces``.  Equal to the
+        gradient when the list is symmetric within the descriptor's range (full lists, no overflow, ``r_cut`` not above the
+        list's cutoff); not checked."""
+        B, NN = self._check(x)
+        if not isinstance(index, torch.Tensor) or tuple(index.shape) != (B, NN) or index.device != x.device:
+            raise ValueError("DescriptorMLP: index must be a [%d, %d] tensor on %s, got %s" % (
+                B, NN, x.device, tuple(index.shape) if isinstance(index, torch.Tensor) else type(index)))
+        if index.dtype != torch.int32:
+            index = torch.round(index.detach()).to(torch.int32) if index.is_floating_point() else index.to(torch.int32)
+        index = index.contiguous()
+        own = None
+        if self.n_types > 1:
+            if types is None:
+                raise ValueError("DescriptorMLP: n_types = %d needs the rows' own types: total_forces(x, index, types=...)"
+                                 % self.n_types)
+            if hasattr(types, "plain"):
+                types = types.plain()
+            if (not isinstance(types, torch.Tensor) or types.device != x.device or tuple(types.shape) not in ((B,), (B, 4))):
+                raise ValueError("DescriptorMLP: types must be a [%d] or [%d, 4] tensor on %s, got %s" % (
+                    B, B, x.device, tuple(types.shape) if isinstance(types, torch.Tensor) else type(types)))
+            own = (types[:, 3] if types.dim() == 2 else types).detach().to(torch.float32).contiguous()
+        out = torch.empty((B, 4), dtype=x.dtype, device=x.device)
+        v = torch.empty((B, 3, 3), dtype=x.dtype, device=x.device) if virial else None
+        g = torch.empty((B, self.D), dtype=torch.float32, device=x.device)
+        e = torch.empty((B,), dtype=torch.float32, device=x.device)
+        act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
+        launches, rows = self._launches(species, x)
+        for _, d_rows, n_rows, d_w in launches:   # pass 1: every row is in exactly one list
+            check(lib.htf_cf_grad(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, d_w,
+                                  self.mu.data_ptr(), float(self.gap), g.data_ptr(), e.data_ptr(), d_rows, n_rows,
+                                  float(self.r_cut or 0.0), ops._stream(x)))
+        check(lib.htf_cf_forces(x.data_ptr(), ops._dt(x), index.data_ptr(), own.data_ptr() if own is not None else None, B, NN,
+                                self.K, self.n_types, self.mu.data_ptr(), float(self.gap), g.data_ptr(), e.data_ptr(),
+                                out.data_ptr(), ops._dt(out), v.data_ptr() if v is not None else None,
+                                float(self.r_cut or 0.0), ops._stream(x)))
+        return (out, v) if virial else out
+
     def loss_gradient(self, x, labels, pred=None, accum=None, species=None):
         """One force-matching sweep (htf_bp_loss_grad) over a pair-vector tensor ``x`` [B, NN, 4] (fp32 or fp64) and
         ``labels`` [B, 4] (fp32 or fp64): returns ``accum`` [1 + P] fp32 on the device, {sum of squared residuals of
@@ -539,7 +598,8 @@ class DescriptorMLP:
             raise ValueError("DescriptorMLP: NN = %d neighbor slots; the kernel takes at most %d" % (nl.shape[1], self.MAX_NN))
         if self.n_species > 1 and positions is None:
             raise ValueError("DescriptorMLP: n_species = %d needs the particles' species: layer(nlist, positions)" % self.n_species)
-        return simmodel.DescriptorEnergy(nl, self, positions if self.n_species > 1 else None)
+        return simmodel.DescriptorEnergy(nl, self, positions if self.n_species > 1 else None,
+                                         positions=positions if self.conservative else None)
 
 
 class EDSLayer:

@@ -204,6 +204,22 @@ def build_pair_vectors(pos, n_neigh, head_list, nlist, box, r_cut, NN, offset=0,
     return out
 
 
+def build_pair_index(pos, n_neigh, head_list, nlist, box, r_cut, NN, offset=0, batch_size=None, n_local=None, periodic=(1, 1, 1)):
+    """The index tensor that goes with ``build_pair_vectors`` on the same arguments (htf_cf_pair_index): int32 [B, NN], slot
+    ``s`` of row ``w`` holds the particle whose pair vector sits in slot ``s`` of that row, -1 for a zero-filled slot."""
+    _dev(pos, "pos")
+    N = int(n_neigh.shape[0]) if n_local is None else int(n_local)
+    B = N - offset if batch_size is None else int(batch_size)
+    out = torch.empty((B, NN), dtype=torch.int32, device=pos.device)
+    if B == 0:
+        return out
+    b = box if isinstance(box, _lib.Box) else _lib.make_box(box, periodic)
+    check(lib.htf_cf_pair_index(out.data_ptr(), pos.data_ptr(), _dt(pos), N, NN, offset, B, C.byref(b),
+                                _u32(n_neigh, "n_neigh").data_ptr(), _u32(nlist, "nlist").data_ptr(),
+                                _u32(head_list, "head_list").data_ptr(), float(r_cut), _stream(pos)))
+    return out
+
+
 def eval_forces(potential, nlist, virial=False, out=None, out_dtype=None, virial_out=None, positions=None):
     """SimModel.compute for a declarative potential: nlist [B,NN,4] -> forces [B,4]
     (fx, fy, fz, energy) and, if ``virial``, the [B,3,3] virial.  ``positions`` ([B,4], the tensor compute() receives beside

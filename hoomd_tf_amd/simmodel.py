@@ -65,10 +65,13 @@ class Nlist(_TorchOperand):
     """The ``N x NN x 4`` neighbor tensor handed to ``compute`` (simmodel.py:99-105):
     a zero-copy view of the pair-vector buffer plus the identity the expression layer
     needs.  ``nlist[:, :, :3]`` stays symbolic for the declarative layers; torch code gets
-    the autograd leaf ``ad``."""
+    the autograd leaf ``ad``.  ``index``: the int32 ``[N, NN]`` tensor of the particle in each slot (-1: empty), or a
+    callable that builds it; it is built when ``.index`` is first read (a conservative DescriptorMLP reads it), None when the
+    list came without one."""
 
-    def __init__(self, tensor):
+    def __init__(self, tensor, index=None):
         self.tensor = tensor
+        self._index = index
         self._ad = None
         self._weights = []      # the scalar weights traced expressions of this list read: [(leaf tensor, flat index), ...] -> p.theta[k]
 
@@ -81,6 +84,12 @@ class Nlist(_TorchOperand):
         if self._ad is None:
             self._ad = self.tensor.detach().requires_grad_(True)
         return self._ad
+
+    @property
+    def index(self):
+        if callable(self._index):
+            self._index = self._index()
+        return self._index
 
     def weight_index(self, leaf, flat):
         """k of (leaf, flat) in this trace's weight vector (appended on first sight)."""
@@ -1428,11 +1437,12 @@ class DescriptorEnergy(PairEnergy):
     """DescriptorMLP(nlist): the per-particle energy [N] of the descriptor network.  compute_nlist_forces evaluates it in one
     kernel (htf_bp_forces) and keeps the step eager.  It does not combine with other energies: arithmetic raises, so a sum
     the kernel cannot form never reaches the forces.  ``species``: the tensor the layer reads the particles' own species from
-    (one network per species, DescriptorMLP(n_species=...)), None for a layer of one network."""
+    (one network per species, DescriptorMLP(n_species=...)), None for a layer of one network.  ``positions``: what
+    ``layer(nlist, positions)`` was given, from which a conservative layer of several types reads the particles' own types."""
     reduced = True
 
-    def __init__(self, nlist, layer, species=None):
-        self.nlist, self.layer, self.species = nlist, layer, species
+    def __init__(self, nlist, layer, species=None, positions=None):
+        self.nlist, self.layer, self.species, self.positions = nlist, layer, species, positions
 
     def key(self):
         return ("descriptor-mlp",)
@@ -1706,7 +1716,20 @@ def compute_nlist_forces(nlist, energy, virial=False):
         if training and not energy.layer.trainable:
             raise NotImplementedError("this DescriptorMLP is not trainable: neither tfcompute(train=True) nor train_on_batch "
                                       "covers a model that holds it (construct it with trainable=True)")
-        out = energy.layer.forces(nl.tensor, virial, species=energy.species)
+        lay = energy.layer
+        if getattr(lay, "conservative", False):
+            # F = -d(sum_i E_i)/dr: the reverse terms need the particle in each slot and, with several types, the rows' own types
+            index = nl.index if nl.index is not None else energy.nlist.index
+            if index is None:
+                raise ValueError("a conservative DescriptorMLP needs the particle index of every neighbor slot: "
+                                 "htf.Nlist(tensor, index=...) (tfcompute provides it for the step's own neighbor list)")
+            if lay.n_types > 1 and energy.positions is None:
+                raise ValueError("a conservative DescriptorMLP with n_types = %d needs the particles' own types: "
+                                 "layer(nlist, positions)" % lay.n_types)
+            types = _unwrap(energy.positions)[:nl.tensor.shape[0]] if lay.n_types > 1 else None
+            out = lay.total_forces(nl.tensor, index, virial, types=types, species=energy.species)
+        else:
+            out = lay.forces(nl.tensor, virial, species=energy.species)
         entry = {"op": "descriptor_mlp", "species": energy.species}   # (no plan: a model calling it keeps the eager path)
         if training:
             # what tfcompute's training step needs (no "potential": the layer's own sweep trains it, DescriptorMLP.loss_gradient)

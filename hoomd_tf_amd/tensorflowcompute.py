@@ -579,6 +579,24 @@ class tfcompute:
         ops.bias_combine(self.force, bp["fb"], eds.state[2:3], bp["cv_value"])
         self._last = (bp["pv"], ops.copy_positions(s.pos, offset=0, N=s.N, unstuff4=True), 0, s.N)
 
+    def _index_provider(self, offset, n):
+        """What ``Nlist.index`` of the step's neighbor tensor calls when it is first read: the particle in each slot
+        (ops.build_pair_index on the arguments of the step's build_pair_vectors).  A conservative DescriptorMLP reads it, and
+        needs g_j of every neighbor in the same call: it raises where some are elsewhere."""
+        def build():
+            s, nl = self.system, self._nlist
+            if n < s.N:
+                raise ValueError("a conservative DescriptorMLP needs the whole system in one batch (batch_size %d < N = %d): "
+                                 "its forces read dE_j/dG_j of every neighbor j" % (n, s.N))
+            if getattr(nl, "domain", None) is not None or getattr(s, "n_ghost", 0):
+                raise ValueError("a conservative DescriptorMLP does not run under domain decomposition: dE_j/dG_j of ghost "
+                                 "particles is not exchanged")
+            if self.model._map_nlist:
+                raise ValueError("a conservative DescriptorMLP does not run on a mapped neighbor list")
+            return ops.build_pair_index(s.pos, nl.n_neigh, nl.head_list, nl.nlist, s.box, self.r_cut, self.nneighbor_cutoff,
+                                        offset=offset, batch_size=n, n_local=s.N)
+        return build
+
     def _finish_update(self, batch_index, offset, n):
         """tensorflowcompute.py:313-345 (inference branch)."""
         if batch_index == 0:
@@ -594,6 +612,8 @@ class tfcompute:
         box_t = torch.as_tensor(s.box3x3, dtype=s.dtype, device=s.device)
         self._last = (nlist_t, pos_t, offset, n)
         inputs = m.compute_inputs(nlist_t, pos_t, box_t)
+        if NN > 0:
+            inputs[0]._index = self._index_provider(offset, n)   # (built only when read: a conservative DescriptorMLP)
         mark = len(simmodel._trace_log())
         simmodel._trace.training_graph = bool(self.train)  # generic route: forces stay differentiable
         try:

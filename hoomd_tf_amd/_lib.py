@@ -286,9 +286,14 @@ CF_PROTOTYPES = {
     "htf_cf_pair_index": (_i, [_vp, _vp, _i, _u, _u, _u, _u, C.POINTER(Box), _vp, _vp, _vp, _d, _vp]),
 }
 
+# force matching on the conservative forces (include/htf_ctrain.h; DescriptorMLP.total_loss_gradient)
+CT_PROTOTYPES = {
+    "htf_ct_loss_grad": (_i, [_vp, _i, _vp, _u, _u, _u, _u, _u, _u, _i, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _u, C.c_float, _vp]),
+}
+
 # every table above: what the ctypes and the pybind11 binding both declare
 ALL_PROTOTYPES = tuple((name, proto) for table in (PROTOTYPES, STANDIN_PROTOTYPES, STEP_CHECK_PROTOTYPES, CG_PROTOTYPES, GEOM_PROTOTYPES, NLIST_PROTOTYPES,
-                                                   BP_PROTOTYPES, CF_PROTOTYPES) for name, proto in table.items())
+                                                   BP_PROTOTYPES, CF_PROTOTYPES, CT_PROTOTYPES) for name, proto in table.items())
 
 
 ABI_VERSION = 5  # include/htf_amd.h HTF_AMD_ABI_VERSION: the struct layouts the ctypes Structures of this file mirror

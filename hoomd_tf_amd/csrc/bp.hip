@@ -50,11 +50,15 @@ __global__ __launch_bounds__(256) void dtrain_reduce_kernel(const float *__restr
     }
 }
 
-// nparts may be 0: accum is then zero-filled
+} // namespace
+
+// nparts may be 0: accum is then zero-filled (declared in htf_internal.h: ctrain.hip's sweep ends in the same reduction)
 int dtrain_reduce_launch(const float *d_partials, unsigned nparts, unsigned n, float *d_accum, hipStream_t stream) {
     hipLaunchKernelGGL(dtrain_reduce_kernel, dim3((n + 63u) / 64u), dim3(256), 0, stream, d_partials, nparts, n, d_accum);
     return check_launch("dtrain_reduce_kernel");
 }
+
+namespace {
 
 int bp_check(unsigned B, unsigned n_rows, float r_cut) {
     HTF_REQUIRE(n_rows <= B, "descriptor network: n_rows %u > B %u", n_rows, B);

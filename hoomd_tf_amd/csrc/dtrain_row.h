@@ -26,6 +26,11 @@
 //   CUT   e_k -> fc(r) e_k, so e_k' a -> (c_der d fc + fc') e_k a; a slot at r >= rc is dropped where the slots are read.
 //   LIST  wave work item q handles row rows[q] instead of row q: the labels and the prediction are read at the row, and q
 //         alone decides which wave and block accumulate it -- entry q is treated as row q of a batch of n.
+// and one of its own:
+//   TOTAL the sweep of the conservative forces (ctrain.hip, include/htf_ctrain.h): rho_i . F_i with F = -d(sum E)/dr regroups,
+//         row by row, into the same directional derivative with a_ij = ((rho_i - rho_j) . t_ij) / r_ij, j = index[i][slot]
+//         (no rho_j for j outside [0, B)).  `pred` is then the residual table rho [B][4], read where the labels and the
+//         prediction were; a live slot reads its index and gathers rho_j as one float4, folded into a at once.
 #ifndef HTF_DTRAIN_ROW_H_
 #define HTF_DTRAIN_ROW_H_
 #include "desc_row.h"   // the limits, the activation and the weights' LDS layout are the evaluator's
@@ -66,11 +71,12 @@ __device__ __forceinline__ void outer_accumulate(float (&acc)[64], const float *
 }
 
 // n work items: rows 0 .. n - 1, or rows[0 .. n - 1] with LIST (rows is then not null); one partial [1 + P] per block
-template <bool TANH, bool CUT, bool LIST, typename IT>
+template <bool TANH, bool CUT, bool LIST, typename IT, bool TOTAL = false>
 __device__ __forceinline__ void dtrain_rows(const typename Vec4<IT>::type *__restrict__ nlist, const int *__restrict__ rows, unsigned n,
                                             unsigned NN, const float *__restrict__ weights, const float *__restrict__ mu, int K, int T,
                                             int H1, int H2, float gap, float rc, const void *__restrict__ labels, int labels_f64,
-                                            const float4 *__restrict__ pred, float *__restrict__ partials) {
+                                            const float4 *__restrict__ pred, float *__restrict__ partials,
+                                            const int *__restrict__ index = nullptr, unsigned B = 0) {
     extern __shared__ float s_mem[];
     const int D = K * T;
     const int ld1 = H1 + 1, ld2 = H2 + 1;   // odd row strides: a column walk (lane a reads W2[a][b]) spreads over the banks
@@ -108,18 +114,20 @@ __device__ __forceinline__ void dtrain_rows(const typename Vec4<IT>::type *__res
         if constexpr (LIST) row = (unsigned)rows[q];
         // 0. the residual (the same value in every lane)
         const float4 pr = pred[row];
-        float lx, ly, lz, lw;
-        if (labels_f64) {
-            const double *lp = (const double *)labels + (size_t)row * 4;
-            lx = (float)lp[0]; ly = (float)lp[1]; lz = (float)lp[2]; lw = (float)lp[3];
-        } else {
-            const float *lp = (const float *)labels + (size_t)row * 4;
-            lx = lp[0]; ly = lp[1]; lz = lp[2]; lw = lp[3];
+        float lx = 0.f, ly = 0.f, lz = 0.f, lw = 0.f;   // (TOTAL: pred is the residual itself)
+        if constexpr (!TOTAL) {
+            if (labels_f64) {
+                const double *lp = (const double *)labels + (size_t)row * 4;
+                lx = (float)lp[0]; ly = (float)lp[1]; lz = (float)lp[2]; lw = (float)lp[3];
+            } else {
+                const float *lp = (const float *)labels + (size_t)row * 4;
+                lx = lp[0]; ly = lp[1]; lz = lp[2]; lw = lp[3];
+            }
         }
         const float rx = pr.x - lx, ry = pr.y - ly, rz = pr.z - lz, re = pr.w - lw;
         assr += (rx * rx + ry * ry) + (rz * rz + re * re);
 
-        // 1. this lane's slots: distance, type (-1: contributes nothing), a = 2 (rho . t) / r
+        // 1. this lane's slots: distance, type (-1: contributes nothing), a = 2 (rho . t) / r (TOTAL: ((rho - rho_j) . t) / r)
         const typename Vec4<IT>::type *rp = nlist + (size_t)row * NN;
         float r[kDescSlots], a[kDescSlots];
         float fc[kDescSlots], dfc[kDescSlots];   // (CUT only)
@@ -145,7 +153,17 @@ __device__ __forceinline__ void dtrain_rows(const typename Vec4<IT>::type *__res
                 if (live) {
                     r[t] = rr;
                     ty[t] = typ;
-                    a[t] = 2.0f * (rx * tx + ry * tyy + rz * tz) / rr;
+                    if constexpr (TOTAL) {
+                        float ax = rx, ay = ry, az = rz;
+                        const int j = index[(size_t)row * NN + slot];
+                        if ((unsigned)j < B) {   // (a negative index is above B as unsigned)
+                            const float4 rj = pred[j];
+                            ax -= rj.x; ay -= rj.y; az -= rj.z;
+                        }
+                        a[t] = (ax * tx + ay * tyy + az * tz) / rr;
+                    } else {
+                        a[t] = 2.0f * (rx * tx + ry * tyy + rz * tz) / rr;
+                    }
                     if constexpr (CUT) cutoff_terms(rr, rc, c_fc, fc[t], dfc[t]);
                 }
             }

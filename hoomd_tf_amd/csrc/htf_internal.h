@@ -169,6 +169,10 @@ int train_list_dispatch(const PotParams &p, const void *pos, int pos_dtype, unsi
                         int label_dtype, void *pred, float *accum, float *scratch, hipStream_t stream);
 int jit_num_params(const JitKernels *k);
 
+// the descriptor network's sweeps (bp.hip, ctrain.hip) end in one reduction kernel, bp.hip's: accum[0 .. n) = the sum of nparts
+// block partials of n floats in a fixed order, entries past the first doubled; nparts = 0 zero-fills
+int dtrain_reduce_launch(const float *d_partials, unsigned nparts, unsigned n, float *d_accum, hipStream_t stream);
+
 // counts (nullable): live slots per row; slots >= counts[row] are known zero padding and not loaded
 int eval_pair_dispatch(const PotParams &p, const void *nlist, int in_dtype, unsigned B, unsigned NN,
                        void *force, int force_dtype, void *virial9, const unsigned *counts, hipStream_t stream);

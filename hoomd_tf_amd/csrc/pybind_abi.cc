@@ -19,6 +19,7 @@
 #include "htf_nlist.h"
 #include "htf_bp.h"
 #include "htf_cforce.h"
+#include "htf_ctrain.h"
 
 namespace py = pybind11;
 
@@ -192,6 +193,10 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
     X(htf_cf_forces) \
     X(htf_cf_pair_index)
 
+// include/htf_ctrain.h: force matching on the conservative forces (_lib.CT_PROTOTYPES)
+#define HTF_CT_FUNCTIONS(X) \
+    X(htf_ct_loss_grad)
+
 PYBIND11_MODULE(_htf_abi, m) {
     m.doc() = "pybind11 binding of libhtf_amd.so's C ABI: pointers as integers";
     // a stale module (or library): this module's templates were instantiated from one header, the library it resolved at load
@@ -208,5 +213,6 @@ PYBIND11_MODULE(_htf_abi, m) {
     HTF_NLIST_FUNCTIONS(X)
     HTF_BP_FUNCTIONS(X)
     HTF_CF_FUNCTIONS(X)
+    HTF_CT_FUNCTIONS(X)
 #undef X
 }

@@ -333,8 +333,14 @@ class DescriptorMLP:
     tensor (both calls produce the same slots).  With ``n_types > 1`` it also needs the rows' own types:
     ``layer(nlist, positions)``.  The forces are exact when the list is symmetric within the descriptor's range -- full
     lists, no overflow, ``r_cut`` not above the list's cutoff -- which is not checked.  Energies are the row operator's, bit
-    for bit.  Not with ``trainable=True`` (the sweep differentiates the row operator), batches, domain decomposition or a
-    mapped list: each raises.
+    for bit.  Not with batches, domain decomposition or a mapped list: each raises.
+
+    ``trainable="total"`` is force matching on those forces (htf_ct_loss_grad, include/htf_ctrain.h) and implies
+    ``conservative=True``: the layer is fitted to the force definition it runs with.  Under ``tfcompute.attach(...,
+    train=True)`` every step is one ``total_loss_gradient`` sweep on the step's own list, index and ``total_forces`` output,
+    and one optimizer step; offline, ``total_loss_gradient(x, labels, index)`` with ``iter_from_trajectory`` and the index
+    above.  The sweep is ``loss_gradient``'s with one gathered residual per slot; it needs no types of the rows' own.
+    ``trainable=True`` with ``conservative=True`` raises: that sweep differentiates the row operator.
     Limits: ``n_types * K <= 64``, ``H1, H2 <= 64``, at most 256 neighbor slots."""
 
     name = 'descriptor-mlp'
@@ -346,10 +352,15 @@ class DescriptorMLP:
     def __init__(self, K=16, H1=32, H2=32, low=0.0, high=3.0, n_types=1, activation="tanh", seed=3, device=None,
                  trainable=False, r_cut=None, n_species=1, conservative=False):
         K, H1, H2, n_types, n_species = int(K), int(H1), int(H2), int(n_types), int(n_species)
-        self.trainable, self.conservative = bool(trainable), bool(conservative)
-        if self.trainable and self.conservative:
-            raise ValueError("DescriptorMLP: conservative=True cannot be trainable: the force-matching sweep differentiates "
-                             "the row operator's forces")
+        if isinstance(trainable, str):
+            if trainable != "total":
+                raise ValueError("DescriptorMLP: trainable must be False, True or 'total', not %r" % (trainable,))
+            self.trainable, self.conservative = "total", True   # the forces of the total energy, fitted and run alike
+        else:
+            self.trainable, self.conservative = bool(trainable), bool(conservative)
+            if self.trainable and self.conservative:
+                raise ValueError("DescriptorMLP: conservative=True cannot go with trainable=True, whose force-matching sweep "
+                                 "differentiates the row operator's forces: trainable=\"total\" fits the conservative forces")
         if r_cut is not None:
             r_cut = float(np.float32(r_cut))
             if not (np.isfinite(r_cut) and r_cut > 0):
@@ -384,7 +395,7 @@ class DescriptorMLP:
         cfg = {'K': self.K, 'H1': self.H1, 'H2': self.H2, 'low': self.low, 'high': self.high, 'n_types': self.n_types,
                'activation': self.activation}
         if self.trainable:
-            cfg['trainable'] = True
+            cfg['trainable'] = self.trainable   # (True or "total")
         if self.r_cut is not None:
             cfg['r_cut'] = self.r_cut
         if self.n_species != 1:
@@ -494,6 +505,17 @@ class DescriptorMLP:
                                     ops._stream(x)))
         return (out, v) if virial else out
 
+    @staticmethod
+    def _slot_index(index, x):
+        """The particle in each slot as a contiguous int32 [B, NN] on ``x``'s device; a float tensor is taken by ``rint``."""
+        B, NN = int(x.shape[0]), int(x.shape[1])
+        if not isinstance(index, torch.Tensor) or tuple(index.shape) != (B, NN) or index.device != x.device:
+            raise ValueError("DescriptorMLP: index must be a [%d, %d] tensor on %s, got %s" % (
+                B, NN, x.device, tuple(index.shape) if isinstance(index, torch.Tensor) else type(index)))
+        if index.dtype != torch.int32:
+            index = torch.round(index.detach()).to(torch.int32) if index.is_floating_point() else index.to(torch.int32)
+        return index.contiguous()
+
     def total_forces(self, x, index, virial=False, types=None, species=None):
         """The forces of the total energy, ``F = -d(sum_i E_i)/dr`` (include/htf_cforce.h), on a pair-vector tensor ``x``
         [B, NN, 4] (fp32 or fp64): [B, 4] in ``x``'s dtype with ``E_i`` (``forces``' bits) in column 3, and with ``virial``
@@ -503,12 +525,7 @@ class DescriptorMLP:
         gradient when the list is symmetric within the descriptor's range (full lists, no overflow, ``r_cut`` not above the
         list's cutoff); not checked."""
         B, NN = self._check(x)
-        if not isinstance(index, torch.Tensor) or tuple(index.shape) != (B, NN) or index.device != x.device:
-            raise ValueError("DescriptorMLP: index must be a [%d, %d] tensor on %s, got %s" % (
-                B, NN, x.device, tuple(index.shape) if isinstance(index, torch.Tensor) else type(index)))
-        if index.dtype != torch.int32:
-            index = torch.round(index.detach()).to(torch.int32) if index.is_floating_point() else index.to(torch.int32)
-        index = index.contiguous()
+        index = self._slot_index(index, x)
         own = None
         if self.n_types > 1:
             if types is None:
@@ -572,6 +589,53 @@ class DescriptorMLP:
             present.add(s)
             check(lib.htf_bp_loss_grad(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, d_w,
                                        self.mu.data_ptr(), float(self.gap), labels.data_ptr(), ops._dt(labels), pred.data_ptr(),
+                                       accum.data_ptr() + 4 * s * (1 + P), scratch.data_ptr(), d_rows, n_rows,
+                                       float(self.r_cut or 0.0), ops._stream(x)))
+        if S > 1:
+            for s in range(S):
+                if s not in present:
+                    accum.view(S, 1 + P)[s].zero_()
+        return accum
+
+    def total_loss_gradient(self, x, labels, index, types=None, pred=None, accum=None, species=None):
+        """One force-matching sweep on the forces of the total energy (htf_ct_loss_grad, include/htf_ctrain.h): ``accum`` as
+        ``loss_gradient`` returns it -- [1 + P], or [S, 1 + P] with zero rows for absent species -- for the residuals of
+        ``total_forces(x, index, ...)`` against ``labels`` [B, 4], so that the fit and a ``conservative=True`` run see the same
+        model.  ``index`` as for ``total_forces``; a slot whose index is outside ``[0, B)`` has no reverse term, as there.
+        ``pred`` [B, 4] fp32: ``total_forces`` at the current weights, evaluated here (with ``types``, which the sweep itself
+        does not need) when not given.  The residual ``pred - labels`` is formed in fp32 with torch and every row's is read:
+        ``x`` holds the whole system.  Two calls on the same inputs give the same bits.  Callable on any layer, like
+        ``total_forces``."""
+        B, NN = self._check(x)
+        index = self._slot_index(index, x)
+        ops._dev(labels, "labels")
+        ops._dt(labels)
+        if tuple(labels.shape) != (B, 4) or labels.device != x.device:
+            raise ValueError("DescriptorMLP: labels must be [%d, 4] on %s, got %s on %s" % (B, x.device, tuple(labels.shape), labels.device))
+        if pred is None:
+            pred = self.total_forces(x, index, types=types, species=species)
+            if pred.dtype != torch.float32:
+                pred = pred.to(torch.float32)
+        ops._dev(pred, "pred", torch.float32)
+        if tuple(pred.shape) != (B, 4) or pred.device != x.device:
+            raise ValueError("DescriptorMLP: pred must be [%d, 4] on %s, got %s on %s" % (B, x.device, tuple(pred.shape), pred.device))
+        rho = (pred.detach() - labels.detach().to(torch.float32)).contiguous()
+        S, P = self.n_species, self.P
+        if accum is None:
+            accum = torch.empty((S, 1 + P) if S > 1 else (1 + P,), dtype=torch.float32, device=x.device)
+        ops._dev(accum, "accum", torch.float32)
+        if accum.numel() != S * (1 + P) or accum.device != x.device:
+            raise ValueError("DescriptorMLP: accum must hold %d floats on %s" % (S * (1 + P), x.device))
+        act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
+        launches, rows = self._launches(species, x)
+        # one scratch buffer for the largest species: the launches run one after the other on the stream
+        scratch = torch.empty(max(1, int(lib.htf_bp_scratch_floats(max([n for _, _, n, _ in launches] or [0]), self.K, self.n_types,
+                                                                   self.H1, self.H2))), dtype=torch.float32, device=x.device)
+        present = set()
+        for s, d_rows, n_rows, d_w in launches:
+            present.add(s)
+            check(lib.htf_ct_loss_grad(x.data_ptr(), ops._dt(x), index.data_ptr(), B, NN, self.K, self.n_types, self.H1, self.H2,
+                                       act, d_w, self.mu.data_ptr(), float(self.gap), rho.data_ptr(),
                                        accum.data_ptr() + 4 * s * (1 + P), scratch.data_ptr(), d_rows, n_rows,
                                        float(self.r_cut or 0.0), ops._stream(x)))
         if S > 1:

@@ -1717,6 +1717,7 @@ def compute_nlist_forces(nlist, energy, virial=False):
             raise NotImplementedError("this DescriptorMLP is not trainable: neither tfcompute(train=True) nor train_on_batch "
                                       "covers a model that holds it (construct it with trainable=True)")
         lay = energy.layer
+        index = types = None
         if getattr(lay, "conservative", False):
             # F = -d(sum_i E_i)/dr: the reverse terms need the particle in each slot and, with several types, the rows' own types
             index = nl.index if nl.index is not None else energy.nlist.index
@@ -1732,8 +1733,9 @@ def compute_nlist_forces(nlist, energy, virial=False):
             out = lay.forces(nl.tensor, virial, species=energy.species)
         entry = {"op": "descriptor_mlp", "species": energy.species}   # (no plan: a model calling it keeps the eager path)
         if training:
-            # what tfcompute's training step needs (no "potential": the layer's own sweep trains it, DescriptorMLP.loss_gradient)
-            entry.update(layer=energy.layer, nlist=nl, forces=out[0] if virial else out)
+            # what tfcompute's training step needs (no "potential": the layer's own sweep trains it, DescriptorMLP.loss_gradient,
+            # or total_loss_gradient on the slot index and the types a conservative layer has just used)
+            entry.update(layer=energy.layer, nlist=nl, forces=out[0] if virial else out, index=index, types=types)
         _trace_log().append(entry)
         return out
     if isinstance(energy, BiasedEnergy):

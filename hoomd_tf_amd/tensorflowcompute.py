@@ -410,8 +410,8 @@ class tfcompute:
 
     def _train_descriptor(self, nlist_t, offset, n, entry):
         """train_on_batch for a model whose forces are one trainable DescriptorMLP: loss and weight gradient in one sweep over
-        the batch's pair vectors (DescriptorMLP.loss_gradient, with the forces the model has just evaluated as the prediction),
-        optimizer step on the layer's flat weights on the device."""
+        the batch's pair vectors (DescriptorMLP.loss_gradient, or total_loss_gradient for trainable="total", with the forces the
+        model has just evaluated as the prediction), optimizer step on the layer's flat weights on the device."""
         domain = getattr(self._nlist, "domain", None)
         if domain is not None and domain.world > 1:
             raise NotImplementedError("training a DescriptorMLP over several ranks is not implemented")
@@ -423,28 +423,36 @@ class tfcompute:
         pred = pred if pred.dtype == torch.float32 else pred.to(torch.float32)
         S = getattr(layer, "n_species", 1)
         if S > 1:
-            return self._train_descriptor_species(nlist_t, offset, n, layer, pred, entry.get("species"))
+            return self._train_descriptor_species(nlist_t, offset, n, layer, pred, entry)
         if self._opt_state is None:
             self._opt_state = torch.zeros(ops.optimizer_state_floats(int(theta.numel())), dtype=torch.float32,
                                           device=self.system.device)
             if m.metrics:
                 m.metrics[0].state = self._opt_state
-        accum = layer.loss_gradient(nlist_t, self._labels[offset:offset + n], pred=pred)
+        accum = self._descriptor_sweep(layer, nlist_t, self._labels[offset:offset + n], pred, entry)
         ops.optimizer_step(theta, accum, 1.0 / (4.0 * float(n)), self._opt_state, self._opt_desc)
 
-    def _train_descriptor_species(self, nlist_t, offset, n, layer, pred, species):
+    @staticmethod
+    def _descriptor_sweep(layer, nlist_t, labels, pred, entry, species=None):
+        """The layer's sweep for the force definition it trains on: the row operator's (trainable=True), or the forces of the
+        total energy (trainable="total") on the slot index and the types the step's own total_forces call used."""
+        if layer.trainable == "total":
+            return layer.total_loss_gradient(nlist_t, labels, entry["index"], types=entry.get("types"), pred=pred, species=species)
+        return layer.loss_gradient(nlist_t, labels, pred=pred, species=species)
+
+    def _train_descriptor_species(self, nlist_t, offset, n, layer, pred, entry):
         """One network per species: one sweep for the batch, then one optimizer step per species present on that species'
         slice of the weights, each with its own optimizer state and the scale 1 / (4 n) of the whole batch (the batch's mean
         squared error is the sum of the species' shares).  A species without rows in the batch is not stepped: its weights and
         its optimizer state stay as they are.  The reported loss is the sum of the species' sums of squared residuals / (4 n)."""
-        m, S, P = self.model, layer.n_species, layer.P
+        m, S, P, species = self.model, layer.n_species, layer.P, entry.get("species")
         if getattr(self, "_opt_states", None) is None:
             self._opt_states = [torch.zeros(ops.optimizer_state_floats(P), dtype=torch.float32, device=self.system.device)
                                 for _ in range(S)]
             self._opt_state = torch.zeros(_lib.OPT_STATE_FLOATS, dtype=torch.float32, device=self.system.device)  # the metric's
             if m.metrics:
                 m.metrics[0].state = self._opt_state
-        accum = layer.loss_gradient(nlist_t, self._labels[offset:offset + n], pred=pred, species=species)
+        accum = self._descriptor_sweep(layer, nlist_t, self._labels[offset:offset + n], pred, entry, species)
         scale = 1.0 / (4.0 * float(n))
         for s, c in enumerate(layer.species_counts(species, nlist_t)):
             if c:

@@ -1,12 +1,15 @@
 """Drives integration/hoomd_shim/ (TensorflowComputeAMD, the HOOMD-side ForceCompute) against the FAKE HOOMD of
 integration/hoomd_stub/ on a GPU and compares every array it leaves in "HOOMD's" m_force / m_virial with the
 htf.Context path (the C ABI called from Python) BIT FOR BIT.  Run by tests/test_gpu_shim.py in a child process:
-    python tests/shim_driver.py <dir with _htf_amd.so and _hoomd_stub.so> <double|single>
+    python tests/shim_driver.py <dir with _htf_amd.so and _hoomd_stub.so> <double|single> [<box as JSON>]
+The optional third argument, {"periodic": [px, py, pz], "tilt": [xy, xz, yz]}, is the box the fake HOOMD reports (default: periodic
+in x, y and z, no tilt -- the run below); with it only the general-box section runs.
 What is exercised is the reference's per-step body, htf/TensorflowCompute.cc:129-216 and :250-301:
 period gate, nlist->compute, updateBox, batch loop, forces written into m_force, virial folded into m_virial at its
 pitch, reference-force labels, the training step, MaxParticleNumberChange, the log quantity, the half-step hook.
 This is a fake HOOMD (no integrator, no cell list of its own): the stand-in driver moves the particles and builds
 the neighbor list, and the fake's ParticleData / NeighborList point at those device arrays."""
+import json
 import os
 import sys
 
@@ -28,6 +31,9 @@ sdt = torch.float32 if single else torch.float64
 assert H.scalar_bytes == (4 if single else 8)
 dev = torch.device("cuda:0")
 R_CUT, NN = 2.5, 64
+BOX = json.loads(sys.argv[3]) if len(sys.argv) > 3 else None
+PERIODIC = [int(p) for p in BOX.get("periodic", [1, 1, 1])] if BOX else [1, 1, 1]
+TILT = [float(t) for t in BOX.get("tilt", [0.0, 0.0, 0.0])] if BOX else [0.0, 0.0, 0.0]
 
 
 def view(ptr, shape, dtype):
@@ -57,7 +63,7 @@ class FakeHoomdRun:
         self.max_n = s.N + 4                      # HOOMD's max N is rarely N: the virial pitch then differs from N too
         self.pdata.setN(s.N, self.max_n, 0)
         half = [float(x) / 2 for x in L]
-        self.pdata.setBox([-h for h in half], half, [0.0, 0.0, 0.0], [1, 1, 1])
+        self.pdata.setBox([-h for h in half], half, TILT, PERIODIC)
         self.net_force = torch.zeros((s.N, 4), dtype=sdt, device=dev)
         self.pdata.setNetForcePtr(self.net_force.data_ptr(), s.N)
         self.hnl = H.NeighborList()
@@ -95,7 +101,7 @@ class FakeHoomdRun:
         return view(self.c.virialPtr(), (6, pitch), sdt), pitch
 
 
-def oracle_check(run, virial, batch_size, what):
+def oracle_check(run, virial, batch_size, what, periodic=(1, 1, 1)):
     """What the shim left in "HOOMD's" m_force (and, from a zeroed m_virial, in m_virial) against the CPU oracle's
     computeForces (oracle/htf_oracle.py, TensorflowCompute.cc:129-216) on the same positions and list: SURVEY 8(c)'s bound
     as stated, plus the named condition term for the virial's cancelling row sums."""
@@ -106,13 +112,14 @@ def oracle_check(run, virial, batch_size, what):
     model = (lambda x: O.lj_model(x.astype(np.float64), virial=True)) if virial else (lambda x: O.lj_model(x.astype(np.float64)))
     ref, vref = O.compute_forces(pos, np.zeros(s.N, np.int32), nlc.n_neigh.cpu().numpy().view(np.uint32),
                                  nlc.head_list.cpu().numpy().view(np.uint32), nlc.nlist.cpu().numpy().view(np.uint32),
-                                 O.make_box(L, dtype=hd), R_CUT, NN, model, batch_size=batch_size, model_dtype=np.float32, virial=virial)
+                                 O.make_box(L, dtype=hd), R_CUT, NN, model, batch_size=batch_size, model_dtype=np.float32, virial=virial,
+                                 periodic=periodic)
     got = run.force().cpu().numpy().astype(np.float64)
     err = np.abs(got - ref)
     # sum_j |f_ij| per row, the scale two fp32 summation orders differ on (tests/test_gpu_parity.py: cancelling_rows)
     pv = O.prepare_neighbors(pos, np.zeros(s.N, np.int32), nlc.n_neigh.cpu().numpy().view(np.uint32),
                              nlc.head_list.cpu().numpy().view(np.uint32), nlc.nlist.cpu().numpy().view(np.uint32),
-                             O.make_box(L, dtype=hd), R_CUT, NN).astype(np.float32).astype(np.float64)
+                             O.make_box(L, dtype=hd), R_CUT, NN, periodic=periodic).astype(np.float32).astype(np.float64)
     sg, tg, rpg, cg = O._rinv_and_grad_factor(pv)
     cond = np.abs(2.0 * O._grad_from_dEds(2.0 * (2.0 * sg ** 6 - 1.0) * (6.0 * sg ** 5), sg, tg, rpg, cg)).sum(axis=(1, 2))[:, None]
     assert np.all(err[:, 3] <= 1e-5 + 2e-5 * np.abs(ref[:, 3])), (what, "energies vs oracle, as stated", float(err[:, 3].max()))
@@ -131,6 +138,61 @@ def context_for(run, virial, batch_size=0, period=1):
                       max_n=run.sysm.N, fused=2)
     return ctx
 
+
+# ------------------------------------------------------------------ 0. a box with an open axis or a tilt (third argument only)
+def _bits(t):
+    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int64)
+
+
+def general_box_section():
+    """getPeriodic() and the tilt factors of HOOMD's BoxDim reach every call (TensorflowComputeAMD.cc updateBox): what the shim
+    leaves in m_force / m_virial on such a box equals the library route on the same arrays with the same htf_box bit for bit,
+    differs from the plain box's result, and its pair-vector tensor is the oracle's for that box.  The particles and the list are
+    the stand-in's (no tilt, periodic): the same arrays through both routes, not a trajectory."""
+    hd = np.float32 if single else np.float64
+    for virial, batch_size in ((True, 0), (False, 300)):
+        run = FakeHoomdRun(batch_size=batch_size)
+        s, nlc = run.sysm, run.nl
+        pot = htf.Potential.lj()
+        run.c.setPotential(pot.handle.value, virial, False, 2)
+        b3 = np.array([s.box3x3[0], s.box3x3[1], TILT])
+        box = _lib.make_box(b3, PERIODIC)
+        v6, pitch = run.virial6()
+        res = {}
+        for key, bx in (("general", box), ("plain", s.box)):
+            ctx = context_for(run, virial, batch_size)
+            ctx.set_potential(pot)
+            f = torch.zeros((s.N, 4), dtype=sdt, device=dev)
+            v = torch.zeros((6, pitch), dtype=sdt, device=dev)
+            ctx.compute_forces(0, ctx.make_arrays(s.pos, s.N, nlc.n_neigh, nlc.head_list, nlc.nlist, bx, f, v if virial else None, pitch))
+            res[key] = (f, v, ctx)
+        run.c.compute(0)
+        torch.cuda.synchronize()
+        assert torch.equal(_bits(run.force()), _bits(res["general"][0])), ("forces differ from the library route", PERIODIC, TILT)
+        assert not torch.equal(_bits(run.force()), _bits(res["plain"][0])), "the box's flags / tilt did not arrive"
+        if virial:
+            assert torch.equal(_bits(v6), _bits(res["general"][1])), "virial differs from the library route"
+        ba = run.c.getBoxArray()
+        assert (ba[2].x, ba[2].y, ba[2].z) == tuple(hd(t) for t in TILT)
+        n_b = s.N if batch_size == 0 else s.N % batch_size or batch_size
+        off = s.N - n_b
+        pv = view(run.c.getNlistBuffer(), (n_b, NN, 4), torch.float32).cpu().numpy()
+        L = [float(s.box3x3[1][i] - s.box3x3[0][i]) for i in range(3)]
+        want = O.prepare_neighbors(s.pos.cpu().numpy()[:, :3].astype(hd), np.zeros(s.N, np.int32), nlc.n_neigh.cpu().numpy().view(np.uint32),
+                                   nlc.head_list.cpu().numpy().view(np.uint32), nlc.nlist.cpu().numpy().view(np.uint32),
+                                   O.make_box(L, tilt=TILT, dtype=hd), R_CUT, NN, offset=off, batch_size=n_b, periodic=PERIODIC)
+        assert np.array_equal(pv, want.astype(np.float32)), "the shim's tensor is not the oracle's for this box"
+        if not any(TILT):   # (an untilted list on a tilted box holds overlapping images: no force bound there)
+            e = oracle_check(run, virial, batch_size, (virial, batch_size, PERIODIC), periodic=PERIODIC)
+            print("OK box periodic=%s virial=%s batch_size=%d (max err vs oracle %.2e)" % (PERIODIC, virial, batch_size, e))
+        else:
+            print("OK box tilt=%s periodic=%s virial=%s batch_size=%d" % (TILT, PERIODIC, virial, batch_size))
+
+
+if BOX is not None:
+    general_box_section()
+    print("ALL OK")
+    sys.exit(0)
 
 # ------------------------------------------------------------------ 1. ten MD steps, forces + virial, bit for bit
 for virial, batch_size, period in ((True, 0, 1), (False, 0, 1), (True, 300, 1), (False, 0, 3)):

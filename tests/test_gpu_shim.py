@@ -29,3 +29,16 @@ def test_shim_runs_against_fake_hoomd(tmp_path, htf, cuda, precision):
                   "OK forces virial=False batch_size=0 period=3", "OK reallocate", "OK training n_ref=0", "OK training n_ref=2",
                   "OK errors"):
         assert piece in r.stdout, r.stdout
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
+@pytest.mark.parametrize("box", ['{"periodic": [1, 1, 0]}', '{"tilt": [-0.4, 0.25, 0.1]}'], ids=["open-z", "tilt-neg"])
+def test_shim_hands_the_box_flags_and_tilt_down(tmp_path, htf, cuda, box):
+    """TensorflowComputeAMD copies HOOMD's getPeriodic() and tilt factors into every call: with a box that is open along z (what
+    a domain-decomposed run reports along a decomposed axis) or tilted within upstream's skew rule, the forces, the virial and the
+    tensor it leaves equal the library route's on the same arrays -- and differ from the plain box's (double precision)."""
+    build_shim(tmp_path, htf._lib.LIB_PATH, single=False)
+    r = subprocess.run([sys.executable, "-u", "-X", "faulthandler", os.path.join(ROOT, "tests", "shim_driver.py"), str(tmp_path), "double", box],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+    assert r.stdout.count("OK box ") == 2, r.stdout

@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+import box_cases
 from helpers import brute_nlist, fcc_lattice, random_nlist
 from oracle import c_oracle
 from oracle import htf_oracle as O
@@ -37,6 +38,40 @@ def test_prepare_neighbors_bit_exact(clib, dtype):
     ref = O.prepare_neighbors(pos, types, nn, head, nl, box, 2.6, 16, offset=5, batch_size=9)
     got = c_oracle.prepare_neighbors(clib, _stuff(pos, types, dtype), nn, head, nl, box, 2.6, 16, offset=5, batch=9)
     np.testing.assert_array_equal(got, ref)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("name", box_cases.BOX_IDS)
+@pytest.mark.parametrize("which", ["F1", "F2", "F3"])
+def test_prepare_neighbors_on_general_boxes(clib, which, name, dtype):
+    """Per-axis ``periodic`` flags and tilt factors (BoxDim::minImage's general form): C restatement == numpy oracle, bit for bit,
+    on the fixtures the GPU tests of the general path use; on the ragged rows also == the line-by-line loops, for the tensor and
+    for the slot-aligned index.  The fixtures' own conditions are asserted here, where no GPU is needed."""
+    box_cases.check_conditions(which, dtype, name)
+    sysm, box, periodic = box_cases.fixture(which, dtype, name)
+    pos, types, L, nn, head, nl = sysm
+    nn, head, nl = (np.ascontiguousarray(a, dtype=np.uint32) for a in (nn, head, nl))
+    p4 = _stuff(pos, types, dtype)
+    if which != "F1":
+        for NN, r_cut in ([(n, box_cases.F2_RCUT) for n in box_cases.F2_NN] if which == "F2" else [(box_cases.F3_NN, box_cases.F3_RCUT)]):
+            ref = O.prepare_neighbors(pos, types, nn, head, nl, box, r_cut, NN, periodic=periodic)
+            got = c_oracle.prepare_neighbors(clib, p4, nn, head, nl, box, r_cut, NN, periodic=periodic)
+            np.testing.assert_array_equal(got, ref)
+        return
+    for NN, r_cut in box_cases.F1_TABLE:
+        for offset, bs in box_cases.F1_BATCHES:
+            ref = O.prepare_neighbors(pos, types, nn, head, nl, box, r_cut, NN, offset=offset, batch_size=bs, periodic=periodic)
+            got = c_oracle.prepare_neighbors(clib, p4, nn, head, nl, box, r_cut, NN, offset=offset, batch=bs, periodic=periodic)
+            np.testing.assert_array_equal(got, ref)
+            loops = O.prepare_neighbors_loops(pos, types, nn, head, nl, box, r_cut, NN, offset=offset, batch_size=bs, periodic=periodic)
+            np.testing.assert_array_equal(loops, ref)
+            # the index restatement the GPU test of build_pair_index compares with: the same slots, holding the entry's particle
+            idx = box_cases.pair_index(sysm, box, periodic, r_cut, NN, offset=offset, batch=bs)
+            filled = idx >= 0
+            np.testing.assert_array_equal(types[idx[filled]].astype(dtype), ref[filled][:, 3])
+            row_of = np.nonzero(filled)[0] + offset
+            np.testing.assert_array_equal(O.min_image(pos[idx[filled]] - pos[row_of], box, periodic), ref[filled][:, :3])
+            assert np.all(ref[~filled] == 0)
 
 
 def test_lj_matches_numpy_oracle(clib):

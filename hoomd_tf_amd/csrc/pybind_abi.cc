@@ -19,6 +19,7 @@
 #include "htf_nlist.h"
 #include "htf_bp.h"
 #include "htf_cforce.h"
+#include "htf_angular.h"
 #include "htf_ctrain.h"
 
 namespace py = pybind11;
@@ -197,6 +198,12 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
 #define HTF_CT_FUNCTIONS(X) \
     X(htf_ct_loss_grad)
 
+// include/htf_angular.h: angular channels on the conservative forces (_lib.ANG_PROTOTYPES)
+#define HTF_ANG_FUNCTIONS(X) \
+    X(htf_ang_grad) \
+    X(htf_ang_forces) \
+    X(htf_ang_descriptor)
+
 PYBIND11_MODULE(_htf_abi, m) {
     m.doc() = "pybind11 binding of libhtf_amd.so's C ABI: pointers as integers";
     // a stale module (or library): this module's templates were instantiated from one header, the library it resolved at load
@@ -214,5 +221,6 @@ PYBIND11_MODULE(_htf_abi, m) {
     HTF_BP_FUNCTIONS(X)
     HTF_CF_FUNCTIONS(X)
     HTF_CT_FUNCTIONS(X)
+    HTF_ANG_FUNCTIONS(X)
 #undef X
 }

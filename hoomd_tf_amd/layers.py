@@ -341,7 +341,16 @@ class DescriptorMLP:
     and one optimizer step; offline, ``total_loss_gradient(x, labels, index)`` with ``iter_from_trajectory`` and the index
     above.  The sweep is ``loss_gradient``'s with one gathered residual per slot; it needs no types of the rows' own.
     ``trainable=True`` with ``conservative=True`` raises: that sweep differentiates the row operator.
-    Limits: ``n_types * K <= 64``, ``H1, H2 <= 64``, at most 256 neighbor slots."""
+
+    ``l_max=1`` or ``2`` (with ``conservative=True``; include/htf_angular.h) adds angular channels: beside ``G`` the network
+    reads ``A_i[c] = |sum_j w u_ij|^2 = sum_jj' w w' cos(theta_jij')`` and, for ``l_max=2``, ``Q_i[c] = ||sum_j w u_ij (outer)
+    u_ij||_F^2 = sum_jj' w w' cos^2(theta_jij')`` per channel ``c = t K + k``, with ``w = fc(r_ij) e_k(r_ij)`` and ``u_ij`` the
+    direction of the pair vector.  The input is ``[G | A | Q]``, ``D = n_types K (1 + l_max)`` values, the weights are
+    ``mlp_params(seed + s, K=D, H1, H2)``, and ``total_forces`` / ``compute_nlist_forces`` / ``descriptor`` run the angular
+    kernels; everything said about ``conservative=True`` holds.  The row operator has no angular form (``forces`` and
+    ``loss_gradient`` raise) and training is not built yet (``trainable`` raises): weights fitted elsewhere on
+    ``descriptor()`` outputs load through ``set_weights`` / ``load_weights``.  ``l_max=0`` is the layer without the argument.
+    Limits: ``n_types * K * (1 + l_max) <= 64``, ``H1, H2 <= 64``, at most 256 neighbor slots."""
 
     name = 'descriptor-mlp'
     _KEYS = ("W1", "b1", "W2", "b2", "W3", "b3")
@@ -350,8 +359,11 @@ class DescriptorMLP:
     l1_reg = (0.0,)
 
     def __init__(self, K=16, H1=32, H2=32, low=0.0, high=3.0, n_types=1, activation="tanh", seed=3, device=None,
-                 trainable=False, r_cut=None, n_species=1, conservative=False):
+                 trainable=False, r_cut=None, n_species=1, conservative=False, l_max=0):
         K, H1, H2, n_types, n_species = int(K), int(H1), int(H2), int(n_types), int(n_species)
+        if isinstance(l_max, bool) or int(l_max) != l_max or int(l_max) not in (0, 1, 2):
+            raise ValueError("DescriptorMLP: l_max must be 0, 1 or 2, not %r" % (l_max,))
+        self.l_max = l_max = int(l_max)
         if isinstance(trainable, str):
             if trainable != "total":
                 raise ValueError("DescriptorMLP: trainable must be False, True or 'total', not %r" % (trainable,))
@@ -361,6 +373,13 @@ class DescriptorMLP:
             if self.trainable and self.conservative:
                 raise ValueError("DescriptorMLP: conservative=True cannot go with trainable=True, whose force-matching sweep "
                                  "differentiates the row operator's forces: trainable=\"total\" fits the conservative forces")
+        if l_max:
+            if self.trainable:
+                raise NotImplementedError("DescriptorMLP: l_max = %d cannot be trained yet: the force-matching sweep on the angular "
+                                          "conservative forces is the follow-up; fit elsewhere on descriptor() outputs and "
+                                          "load the weights with set_weights / load_weights" % l_max)
+            if not self.conservative:
+                raise ValueError("DescriptorMLP: l_max = %d needs conservative=True: the row operator has no angular form" % l_max)
         if r_cut is not None:
             r_cut = float(np.float32(r_cut))
             if not (np.isfinite(r_cut) and r_cut > 0):
@@ -375,6 +394,9 @@ class DescriptorMLP:
             raise ValueError("DescriptorMLP: K = %d; the Gaussian width is the spacing of at least two centres" % K)
         if n_types < 1 or n_types * K > self.MAX_D:
             raise ValueError("DescriptorMLP: n_types * K = %d * %d channels; the kernel takes 1 to %d" % (n_types, K, self.MAX_D))
+        if n_types * K * (1 + l_max) > self.MAX_D:
+            raise ValueError("DescriptorMLP: n_types * K * (1 + l_max) = %d * %d * %d network inputs; the kernel takes 1 to %d"
+                             % (n_types, K, 1 + l_max, self.MAX_D))
         if not (1 <= H1 <= self.MAX_H and 1 <= H2 <= self.MAX_H):
             raise ValueError("DescriptorMLP: hidden widths %d, %d outside [1, %d]" % (H1, H2, self.MAX_H))
         rbf = RBFExpansion(low, high, K)
@@ -382,7 +404,8 @@ class DescriptorMLP:
             raise ValueError("DescriptorMLP: high = %g must exceed low = %g" % (rbf.high, rbf.low))
         self.K, self.H1, self.H2, self.n_types, self.activation = K, H1, H2, n_types, activation
         self.low, self.high, self.centers, self.gap = rbf.low, rbf.high, rbf.centers, rbf.gap
-        self.D = n_types * K
+        self.Dr = n_types * K                 # radial channels; the network reads [G | A | Q]
+        self.D = self.Dr * (1 + l_max)
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
         ps = [mlp_params(seed=seed + s, K=self.D, H1=H1, H2=H2) for s in range(n_species)]
@@ -402,6 +425,8 @@ class DescriptorMLP:
             cfg['n_species'] = self.n_species
         if self.conservative:
             cfg['conservative'] = True
+        if self.l_max:
+            cfg['l_max'] = self.l_max
         return cfg
 
     def get_weights(self):
@@ -493,6 +518,7 @@ class DescriptorMLP:
         """The kernel on a pair-vector tensor ``x`` [B, NN, 4] (fp32 or fp64): forces [B, 4] in ``x``'s dtype, and the
         [B, 3, 3] virial when ``virial``.  compute_nlist_forces calls this for the layer's energy.  ``species``: [B] or
         [B, 4] (column 3), needed when ``n_species > 1``."""
+        self._no_angular("forces")
         B, NN = self._check(x)
         out = torch.empty((B, 4), dtype=x.dtype, device=x.device)
         v = torch.empty((B, 3, 3), dtype=x.dtype, device=x.device) if virial else None
@@ -504,6 +530,11 @@ class DescriptorMLP:
                                     v.data_ptr() if v is not None else None, d_rows, n_rows, float(self.r_cut or 0.0),
                                     ops._stream(x)))
         return (out, v) if virial else out
+
+    def _no_angular(self, what):
+        if self.l_max:
+            raise ValueError("DescriptorMLP: %s() is the row operator's, which has no angular form (l_max = %d): "
+                             "total_forces(x, index) evaluates this layer" % (what, self.l_max))
 
     @staticmethod
     def _slot_index(index, x):
@@ -539,10 +570,21 @@ class DescriptorMLP:
             own = (types[:, 3] if types.dim() == 2 else types).detach().to(torch.float32).contiguous()
         out = torch.empty((B, 4), dtype=x.dtype, device=x.device)
         v = torch.empty((B, 3, 3), dtype=x.dtype, device=x.device) if virial else None
-        g = torch.empty((B, self.D), dtype=torch.float32, device=x.device)
         e = torch.empty((B,), dtype=torch.float32, device=x.device)
         act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
         launches, rows = self._launches(species, x)
+        if self.l_max:   # include/htf_angular.h: the table {g, p, S} per row and channel in place of g
+            h = torch.empty((B, self.Dr, 4 if self.l_max == 1 else 10), dtype=torch.float32, device=x.device)
+            for _, d_rows, n_rows, d_w in launches:
+                check(lib.htf_ang_grad(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, d_w,
+                                       self.mu.data_ptr(), float(self.gap), h.data_ptr(), e.data_ptr(), d_rows, n_rows,
+                                       float(self.r_cut or 0.0), self.l_max, ops._stream(x)))
+            check(lib.htf_ang_forces(x.data_ptr(), ops._dt(x), index.data_ptr(), own.data_ptr() if own is not None else None, B,
+                                     NN, self.K, self.n_types, self.mu.data_ptr(), float(self.gap), h.data_ptr(), e.data_ptr(),
+                                     out.data_ptr(), ops._dt(out), v.data_ptr() if v is not None else None,
+                                     float(self.r_cut or 0.0), self.l_max, ops._stream(x)))
+            return (out, v) if virial else out
+        g = torch.empty((B, self.D), dtype=torch.float32, device=x.device)
         for _, d_rows, n_rows, d_w in launches:   # pass 1: every row is in exactly one list
             check(lib.htf_cf_grad(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, d_w,
                                   self.mu.data_ptr(), float(self.gap), g.data_ptr(), e.data_ptr(), d_rows, n_rows,
@@ -561,6 +603,7 @@ class DescriptorMLP:
         when not given.  Two calls on the same inputs give the same bits.  With ``n_species = S > 1`` (``species`` as for
         ``forces``) ``accum`` is [S, 1 + P]: row ``s`` holds the residuals and the gradient of network ``s`` over species
         ``s``'s rows, zeros when it has none; each row steps its own slice of ``w``."""
+        self._no_angular("loss_gradient")
         B, NN = self._check(x)
         ops._dev(labels, "labels")
         ops._dt(labels)
@@ -606,6 +649,9 @@ class DescriptorMLP:
         does not need) when not given.  The residual ``pred - labels`` is formed in fp32 with torch and every row's is read:
         ``x`` holds the whole system.  Two calls on the same inputs give the same bits.  Callable on any layer, like
         ``total_forces``."""
+        if self.l_max:
+            raise NotImplementedError("DescriptorMLP: force matching with l_max = %d is the follow-up to the angular channels"
+                                      % self.l_max)
         B, NN = self._check(x)
         index = self._slot_index(index, x)
         ops._dev(labels, "labels")
@@ -645,10 +691,16 @@ class DescriptorMLP:
         return accum
 
     def descriptor(self, nlist):
-        """G [B, D] alone (the kernel's first stage), in the dtype of the pair-vector tensor."""
+        """The network input [B, D] alone (the kernel's first stage), in the dtype of the pair-vector tensor: G, or
+        [G | A | Q] with ``l_max > 0``."""
         x = simmodel._as_nlist(nlist).tensor
         B, NN = self._check(x)
         out = torch.empty((B, self.D), dtype=x.dtype, device=x.device)
+        if self.l_max:
+            check(lib.htf_ang_descriptor(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.mu.data_ptr(), float(self.gap),
+                                         out.data_ptr(), ops._dt(out), float(self.r_cut or 0.0), self.l_max, ops._stream(x)))
+            simmodel._trace_log().append({"op": "descriptor"})
+            return out
         check(lib.htf_bp_descriptor(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.mu.data_ptr(), float(self.gap),
                                     out.data_ptr(), ops._dt(out), float(self.r_cut or 0.0), ops._stream(x)))
         simmodel._trace_log().append({"op": "descriptor"})   # (no replay: a model calling it keeps the eager path)

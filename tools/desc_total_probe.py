@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times the two sweeps of the descriptor network's conservative forces beside the row operator, at the C3 shape.
 
-Usage:  python tools/desc_total_probe.py [--n 131072] [--nn 128] [--iters 20] [--warmup 5] [--r-cut RC] [--window W] [--json PATH]
+Usage:  python tools/desc_total_probe.py [--n 131072] [--nn 128] [--iters 20] [--warmup 5] [--r-cut RC] [--window W] [--l-max L] [--json PATH]
 
 N rows x NN slots, K = 16 channels, 32 x 32 tanh, one type.  HIP events around each launch, the median of --iters launches
 after --warmup, all in one process on one device:
@@ -11,6 +11,9 @@ after --warmup, all in one process on one device:
 Pass 2 is timed twice: with the slots' particles within --window rows of their own row (what a spatially sorted system
 gives; default 4096) and drawn from the whole table (the worst case for the gather: N * D * 4 bytes, 8 MB here).
 Prints one JSON line; ((b) + (c)) / (a) is what the conservative forces cost over the row operator's.
+--l-max 1 or 2 times the angular kernels instead (include/htf_angular.h): pass 1 htf_ang_grad, which writes the table of
+4 or 10 floats per row and channel, and pass 2 htf_ang_forces, which gathers K of those records per slot; the row operator
+has no angular form, so (a) is left out.  --l-max 0 (the default) is the radial path above.
 """
 import argparse
 import json
@@ -48,6 +51,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--r-cut", type=float, default=None)
     ap.add_argument("--window", type=int, default=4096)
+    ap.add_argument("--l-max", type=int, default=0, choices=(0, 1, 2))
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -62,29 +66,42 @@ def main():
     rows = torch.arange(N, device=dev)[:, None]
     near = ((rows + torch.randint(-a.window, a.window + 1, (N, NN), device=dev, generator=g)) % N).to(torch.int32).contiguous()
     far = torch.randint(0, N, (N, NN), device=dev, generator=g).to(torch.int32).contiguous()
-    lay = htf.DescriptorMLP(K=K, H1=H, H2=H, seed=9, conservative=True, **({"r_cut": a.r_cut} if a.r_cut is not None else {}))
-    gbuf = torch.empty((N, lay.D), dtype=torch.float32, device=dev)
+    lay = htf.DescriptorMLP(K=K, H1=H, H2=H, seed=9, conservative=True, **({"r_cut": a.r_cut} if a.r_cut is not None else {}),
+                            **({"l_max": a.l_max} if a.l_max else {}))
+    lm = a.l_max
+    gbuf = torch.empty((N, lay.D) if lm == 0 else (N, K, 4 if lm == 1 else 10), dtype=torch.float32, device=dev)
     ebuf = torch.empty((N,), dtype=torch.float32, device=dev)
     out_t = torch.empty((N, 4), dtype=torch.float32, device=dev)
     rc, stream = float(lay.r_cut or 0.0), ops._stream(x)
 
     def pass1():
+        if lm:
+            _lib.check(_lib.lib.htf_ang_grad(x.data_ptr(), _lib.HTF_F32, N, NN, K, 1, H, H, _lib.ACT_TANH, lay.w.data_ptr(),
+                                             lay.mu.data_ptr(), float(lay.gap), gbuf.data_ptr(), ebuf.data_ptr(), None, N, rc, lm, stream))
+            return
         _lib.check(_lib.lib.htf_cf_grad(x.data_ptr(), _lib.HTF_F32, N, NN, K, 1, H, H, _lib.ACT_TANH, lay.w.data_ptr(), lay.mu.data_ptr(),
                                         float(lay.gap), gbuf.data_ptr(), ebuf.data_ptr(), None, N, rc, stream))
 
     def pass2(index):
+        if lm:
+            _lib.check(_lib.lib.htf_ang_forces(x.data_ptr(), _lib.HTF_F32, index.data_ptr(), None, N, NN, K, 1, lay.mu.data_ptr(),
+                                               float(lay.gap), gbuf.data_ptr(), ebuf.data_ptr(), out_t.data_ptr(), _lib.HTF_F32, None, rc,
+                                               lm, stream))
+            return
         _lib.check(_lib.lib.htf_cf_forces(x.data_ptr(), _lib.HTF_F32, index.data_ptr(), None, N, NN, K, 1, lay.mu.data_ptr(),
                                           float(lay.gap), gbuf.data_ptr(), ebuf.data_ptr(), out_t.data_ptr(), _lib.HTF_F32, None, rc,
                                           stream))
 
     out = {"shape": {"N": N, "NN": NN, "K": K, "H1": H, "H2": H, "activation": "tanh"}, "iters": a.iters, "warmup": a.warmup,
-           "r_cut": a.r_cut, "window": a.window, "device": torch.cuda.get_device_name(0)}
-    out["forces_ms"] = timed(lambda: lay.forces(x), a.iters, a.warmup)
+           "r_cut": a.r_cut, "window": a.window, "l_max": lm, "table_bytes": gbuf.numel() * 4, "device": torch.cuda.get_device_name(0)}
+    if lm == 0:
+        out["forces_ms"] = timed(lambda: lay.forces(x), a.iters, a.warmup)
     out["pass1_ms"] = timed(pass1, a.iters, a.warmup)
     out["pass2_ms"] = timed(lambda: pass2(near), a.iters, a.warmup)
     out["pass2_whole_table_ms"] = timed(lambda: pass2(far), a.iters, a.warmup)
     out["total_forces_ms"] = timed(lambda: lay.total_forces(x, near), a.iters, a.warmup)
-    out["two_passes_over_forces"] = (out["pass1_ms"][0] + out["pass2_ms"][0]) / out["forces_ms"][0]
+    if lm == 0:
+        out["two_passes_over_forces"] = (out["pass1_ms"][0] + out["pass2_ms"][0]) / out["forces_ms"][0]
     out["note"] = "(median, min, max) in ms; one run on one device"
     line = json.dumps(out)
     print(line)

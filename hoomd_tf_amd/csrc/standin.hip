@@ -363,15 +363,25 @@ __device__ __forceinline__ double bperm_t(unsigned lane_idx, double v) {
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 constexpr int kCellBatch = 8; // particles of a cell tested per pass over its candidates (a fine-grid cell holds ~4)
+constexpr unsigned kMapBits = 2048u; // candidates of a walk whose runs are found without a search (round 9, below)
 
+// Round 9: more resident waves, fewer instructions.  A wave of this kernel waits for 59 % of its life and what hides a wait is
+// another wave; with its 106 scalar registers six workgroups fitted a CU, with 80 eight do (forcing the parent's code under
+// that cap, 38 registers spilled, already took 6 us off a rebuild).  So what a batch keeps per particle no longer costs a scalar
+// register or a saved 64-bit branch mask each: "has a row" and "type side" are one bit of a scalar word, tested per trip; the
+// hit count sits in a vector register (the same value in every lane: mbcnt wants it there anyway); the particle's own index is
+// not kept at all -- a candidate is particle p itself where its slot of the sorted copy is the batch's first + p, a compare
+// against an inline constant.  And the run of a candidate comes from a bitmap instead of a search.  (Measured and left out,
+// HISTORY.md: the rows staged in LDS, the next trip's load issued a trip ahead, the self bit cleared by scalar code.)
 template <typename T, bool SHIFT>
-__global__ __launch_bounds__(256) void build_nlist_cells_kernel(const typename Vec4<T>::type *__restrict__ pos_sorted, unsigned N,
-                                                                SBox<T> b, T rl2, unsigned ncell, int nrow,
-                                                                const unsigned *__restrict__ cell_start, unsigned pitch,
-                                                                int type_split, unsigned *__restrict__ n_neigh,
-                                                                unsigned *__restrict__ head_list, unsigned *__restrict__ nlist,
-                                                                unsigned *__restrict__ max_neigh,
-                                                                const uint4 *__restrict__ ranges, unsigned split, Gate gate) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80)))
+void build_nlist_cells_kernel(const typename Vec4<T>::type *__restrict__ pos_sorted, unsigned N,
+                              SBox<T> b, T rl2, unsigned ncell, int nrow,
+                              const unsigned *__restrict__ cell_start, unsigned pitch,
+                              int type_split, unsigned *__restrict__ n_neigh,
+                              unsigned *__restrict__ head_list, unsigned *__restrict__ nlist,
+                              unsigned *__restrict__ max_neigh,
+                              const uint4 *__restrict__ ranges, unsigned split, Gate gate) {
     if (gate.closed()) return;
     using V4 = typename Vec4<T>::type;
     const unsigned lane = threadIdx.x & 63u;
@@ -415,6 +425,33 @@ __global__ __launch_bounds__(256) void build_nlist_cells_kernel(const typename V
     const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
     const bool any_shift = SHIFT && ballot64(len != 0u && (shx != (T)0 || shy != (T)0 || shz != (T)0)) != 0ull;
 
+    // ---- the run of candidate q without a search (a walk of up to kMapBits candidates; a longer one keeps the search).  The
+    // non-empty runs, numbered in walk order, sit compacted in the low lanes: beg - start, and the lane the run came from, for its
+    // shift.  A bitmap over the walk numbering holds a mark at start - 1 of every non-empty run but the first, lane w its 64-bit
+    // word w (wave-private LDS only to OR the marks together; no barrier: a wave's LDS operations complete in order).  The
+    // number of the run of q is then the number of marks below q: those of the words before the trip's, counted as the trips go
+    // by, plus mbcnt of the trip's own word -- two lane reads, two mbcnt and ONE ds_bpermute where the search takes seven
+    // dependent ones and ~35 vector instructions.
+    __shared__ unsigned s_map[4 * (kMapBits / 32u)];
+    unsigned *const map = s_map + (threadIdx.x >> 6) * (kMapBits / 32u);
+    const bool mapped = total <= kMapBits;
+    unsigned delta_c = 0u, lane_c = 0u, map_lo = 0u, map_hi = 0u;
+    if (mapped) { // wave-uniform
+        const unsigned long long runs = ballot64(len != 0u);
+        const unsigned ord = __builtin_amdgcn_mbcnt_hi((unsigned)(runs >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)runs, 0u));
+        const unsigned to = (len != 0u ? ord : 63u) << 2; // (<= 50 runs: lane 63 is nobody's number)
+        delta_c = (unsigned)__builtin_amdgcn_ds_permute((int)to, (int)(beg - start));
+        lane_c = (unsigned)__builtin_amdgcn_ds_permute((int)to, (int)lane);
+        map[lane] = 0u;
+        __builtin_amdgcn_wave_barrier();
+        if (len != 0u && start != 0u) atomicOr(&map[(start - 1u) >> 5], 1u << ((start - 1u) & 31u));
+        __builtin_amdgcn_wave_barrier();
+        map_lo = map[(2u * lane) & 63u];
+        map_hi = map[(2u * lane + 1u) & 63u];
+    }
+    unsigned marks = 0u; // marks in the words before the next trip's
+
+    const T rl2_v = in_vgpr(rl2);
     for (unsigned pb = p_begin + b0 * (unsigned)kCellBatch; pb < p_end; pb += split * (unsigned)kCellBatch) {
         const unsigned np = min(p_end - pb, (unsigned)kCellBatch);
         // the batch's particles: lane p loads particle p, then everything about it becomes wave-uniform
@@ -423,51 +460,69 @@ __global__ __launch_bounds__(256) void build_nlist_cells_kernel(const typename V
         set_tag(me.w, ~0u);
         if (lane < np) me = pos_sorted[pb + lane];
         const unsigned my_tag = (unsigned)scalar_as_int(me.w);
-        if (ballot64(lane < np && (my_tag & ~kTagSide) < N) == 0ull) continue; // a batch of ghosts
-        unsigned tag_p[kCellBatch], count[kCellBatch];
+        // bit p: particle p of the batch has a row (not past the batch, not a ghost: candidates for others, no row of its own)
+        const unsigned rows = (unsigned)ballot64(lane < np && (my_tag & ~kTagSide) < N);
+        if (rows == 0u) continue; // a batch of ghosts
+        const unsigned sides = (unsigned)ballot64((my_tag & kTagSide) != 0u); // bit p: its type is on the far side of type_split
+        unsigned count_v[kCellBatch]; // hits so far, in every lane
         T px[kCellBatch], py[kCellBatch], pz[kCellBatch];
         unsigned row_p[kCellBatch]; // first slot of the particle's row (head_list[i] = i * pitch: 32 bits, as the list's own index)
 #pragma unroll
         for (int p = 0; p < kCellBatch; ++p) {
-            tag_p[p] = ~0u; // (past the batch: index >= N, skipped like a ghost)
+            count_v[p] = 0u;
             px[p] = py[p] = pz[p] = (T)0;
-            count[p] = 0u;
-            row_p[p] = 0u;
+            // (unconditional: a value that may also be zero would be kept per lane; past the batch it is never used)
+            row_p[p] = ((unsigned)__builtin_amdgcn_readlane((int)my_tag, p) & ~kTagSide) * pitch;
             if ((unsigned)p < np) { // wave-uniform
-                tag_p[p] = (unsigned)__builtin_amdgcn_readlane((int)my_tag, p);
+                count_v[p] = __float_as_uint(in_vgpr(0.f));
                 px[p] = in_vgpr(bcast_lane_t(me.x, p));
                 py[p] = in_vgpr(bcast_lane_t(me.y, p));
                 pz[p] = in_vgpr(bcast_lane_t(me.z, p));
-                row_p[p] = (tag_p[p] & ~kTagSide) * pitch;
             }
         }
+        marks = 0u;
         for (unsigned q0 = 0; q0 < total; q0 += 64u) {
-            // ---- which run does candidate q belong to: the last lane whose start is <= q
+            // ---- which run does candidate q belong to
             const unsigned q = q0 + lane;
-            unsigned at = 0u;
+            unsigned at = 0u, src;
+            if (mapped) { // wave-uniform
+                const unsigned w_lo = (unsigned)__builtin_amdgcn_readlane((int)map_lo, (int)(q0 >> 6));
+                const unsigned w_hi = (unsigned)__builtin_amdgcn_readlane((int)map_hi, (int)(q0 >> 6));
+                const unsigned r = __builtin_amdgcn_mbcnt_hi(w_hi, __builtin_amdgcn_mbcnt_lo(w_lo, marks));
+                marks += (unsigned)__builtin_popcount(w_lo) + (unsigned)__builtin_popcount(w_hi);
+                src = q + bperm_u(r, delta_c);
+                if (any_shift) at = bperm_u(r, lane_c);
+            } else { // the last lane whose start is <= q
 #pragma unroll
-            for (unsigned step = 32u; step != 0u; step >>= 1) {
-                const unsigned t = at + step;
-                at = bperm_u(t, start) <= q ? t : at;
+                for (unsigned step = 32u; step != 0u; step >>= 1) {
+                    const unsigned t = at + step;
+                    at = bperm_u(t, start) <= q ? t : at;
+                }
+                src = bperm_u(at, beg) + (q - bperm_u(at, start));
             }
-            const bool valid = q < total;
-            const unsigned src = bperm_u(at, beg) + (q - bperm_u(at, start));
             V4 pk;
             pk.x = pk.y = pk.z = (T)0;
             set_tag(pk.w, ~0u);
-            if (valid) pk = pos_sorted[src];
+            if (q < total) pk = pos_sorted[src];
             if (any_shift) { // wave-uniform: cells within two of a periodic face
                 pk.x -= bperm_t(at, shx);
                 pk.y -= bperm_t(at, shy);
                 pk.z -= bperm_t(at, shz);
             }
+            // a candidate is particle p of the batch itself where its slot of the sorted copy is pb + p (every binned particle
+            // sits in the copy once, the cell's own in the main run of the home stencil row)
+            const unsigned slot = src - pb;
             const unsigned tag = (unsigned)scalar_as_int(pk.w);
             const unsigned k = tag & ~kTagSide;
-            const unsigned long long vmask = ballot64(valid);
+            const unsigned nq = total - q0; // candidates from q0 on: the first min(nq, 64) lanes hold one
+            const unsigned long long vmask = nq >= 64u ? ~0ull : (1ull << nq) - 1ull;
+            const unsigned long long far = type_split >= 0 ? ballot64((tag & kTagSide) != 0u) : 0ull;
+            // (opaque per trip: hoisted out of the loop, the sixteen bit tests below become sixteen saved 64-bit masks)
+            unsigned rows_t = rows, sides_t = sides;
+            asm volatile("" : "+s"(rows_t), "+s"(sides_t));
 #pragma unroll
             for (int p = 0; p < kCellBatch; ++p) {
-                const unsigned i = tag_p[p] & ~kTagSide;
-                if (i >= N) continue; // wave-uniform: past the batch, or a ghost (candidates for others, no row of its own)
+                if (__builtin_expect(((rows_t >> p) & 1u) == 0u, 0)) continue; // wave-uniform
                 T ddx = pk.x - px[p], ddy = pk.y - py[p], ddz = pk.z - pz[p];
                 if (!SHIFT) {
                     ddx = mimg<T>(ddx, b.L[0], b.Linv[0], b.periodic[0]);
@@ -475,19 +530,19 @@ __global__ __launch_bounds__(256) void build_nlist_cells_kernel(const typename V
                     ddz = mimg<T>(ddz, b.L[2], b.Linv[2], b.periodic[2]);
                 }
                 // (no branch: the verdict is the AND of single-compare wave masks, as in the walk above)
-                unsigned long long hits = vmask & ballot64(k != i) & ballot64(ddx * ddx + ddy * ddy + ddz * ddz <= rl2);
-                if (type_split >= 0) { // wave-uniform
-                    asm volatile("" ::: "memory");
-                    hits &= ballot64(((tag ^ tag_p[p]) & kTagSide) == 0u);
+                unsigned long long hits = vmask & ballot64(slot != (unsigned)p) & ballot64(ddx * ddx + ddy * ddy + ddz * ddz <= rl2_v);
+                if (__builtin_expect(type_split >= 0, 0)) { // wave-uniform: the same side only
+                    asm volatile("" ::: "memory"); // (keeps this a branch: as a select it is seven scalar instructions for everybody)
+                    hits &= ((sides_t >> p) & 1u) != 0u ? far : ~far;
                 }
-                const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(hits >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)hits, count[p]));
+                const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(hits >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)hits, count_v[p]));
                 if (inverse_ballot64(hits) && rank < pitch) nlist[row_p[p] + rank] = k;
-                count[p] += (unsigned)__builtin_popcountll(hits);
+                count_v[p] += (unsigned)__builtin_popcountll(hits);
             }
         }
         unsigned cnt = 0u;
 #pragma unroll
-        for (int p = 0; p < kCellBatch; ++p) cnt = lane == (unsigned)p ? count[p] : cnt;
+        for (int p = 0; p < kCellBatch; ++p) cnt = lane == (unsigned)p ? count_v[p] : cnt;
         if (lane < np) {
             const unsigned i = my_tag & ~kTagSide;
             if (i < N) {

@@ -9,7 +9,8 @@ hand-written HIP kernels of ``libhtf_amd.so`` (C ABI: include/htf_amd.h; the coa
 network ``DescriptorMLP``, its force-matching sweep, smooth cutoff and one network per particle species: include/htf_bp.h; its conservative forces ``F = -d(sum_i E_i)/dr``,
 ``DescriptorMLP(conservative=True)``, and the slot-aligned index tensor ``Nlist.index`` they read: include/htf_cforce.h; force
 matching on those forces, ``DescriptorMLP(trainable="total")`` and ``total_loss_gradient``: include/htf_ctrain.h; angular channels on the conservative
-forces, ``DescriptorMLP(conservative=True, l_max=1 or 2)``: include/htf_angular.h).
+forces, ``DescriptorMLP(conservative=True, l_max=1 or 2)``: include/htf_angular.h; force matching on those, ``DescriptorMLP(l_max=1 or 2,
+trainable="angular")`` and ``angular_loss_gradient``: include/htf_atrain.h).
 The offline path ``iter_from_trajectory`` / ``ArrayTrajectory`` runs a
 ``SimModel`` over stored frames.
 """

@@ -298,9 +298,14 @@ ANG_PROTOTYPES = {
     "htf_ang_descriptor": (_i, [_vp, _i, _u, _u, _u, _u, _vp, C.c_float, _vp, _i, C.c_float, _u, _vp]),
 }
 
+# force matching on the angular conservative forces (include/htf_atrain.h; DescriptorMLP.angular_loss_gradient)
+AT_PROTOTYPES = {
+    "htf_at_loss_grad": (_i, [_vp, _i, _vp, _u, _u, _u, _u, _u, _u, _i, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _u, C.c_float, _u, _vp]),
+}
+
 # every table above: what the ctypes and the pybind11 binding both declare
 ALL_PROTOTYPES = tuple((name, proto) for table in (PROTOTYPES, STANDIN_PROTOTYPES, STEP_CHECK_PROTOTYPES, CG_PROTOTYPES, GEOM_PROTOTYPES, NLIST_PROTOTYPES,
-                                                   BP_PROTOTYPES, CF_PROTOTYPES, CT_PROTOTYPES, ANG_PROTOTYPES) for name, proto in table.items())
+                                                   BP_PROTOTYPES, CF_PROTOTYPES, CT_PROTOTYPES, ANG_PROTOTYPES, AT_PROTOTYPES) for name, proto in table.items())
 
 
 ABI_VERSION = 5  # include/htf_amd.h HTF_AMD_ABI_VERSION: the struct layouts the ctypes Structures of this file mirror

@@ -21,6 +21,7 @@
 #include "htf_cforce.h"
 #include "htf_angular.h"
 #include "htf_ctrain.h"
+#include "htf_atrain.h"
 
 namespace py = pybind11;
 
@@ -204,6 +205,10 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
     X(htf_ang_forces) \
     X(htf_ang_descriptor)
 
+// include/htf_atrain.h: force matching on the angular conservative forces (_lib.AT_PROTOTYPES)
+#define HTF_AT_FUNCTIONS(X) \
+    X(htf_at_loss_grad)
+
 PYBIND11_MODULE(_htf_abi, m) {
     m.doc() = "pybind11 binding of libhtf_amd.so's C ABI: pointers as integers";
     // a stale module (or library): this module's templates were instantiated from one header, the library it resolved at load
@@ -222,5 +227,6 @@ PYBIND11_MODULE(_htf_abi, m) {
     HTF_CF_FUNCTIONS(X)
     HTF_CT_FUNCTIONS(X)
     HTF_ANG_FUNCTIONS(X)
+    HTF_AT_FUNCTIONS(X)
 #undef X
 }

@@ -348,8 +348,16 @@ class DescriptorMLP:
     direction of the pair vector.  The input is ``[G | A | Q]``, ``D = n_types K (1 + l_max)`` values, the weights are
     ``mlp_params(seed + s, K=D, H1, H2)``, and ``total_forces`` / ``compute_nlist_forces`` / ``descriptor`` run the angular
     kernels; everything said about ``conservative=True`` holds.  The row operator has no angular form (``forces`` and
-    ``loss_gradient`` raise) and training is not built yet (``trainable`` raises): weights fitted elsewhere on
-    ``descriptor()`` outputs load through ``set_weights`` / ``load_weights``.  ``l_max=0`` is the layer without the argument.
+    ``loss_gradient`` raise, as do ``trainable=True`` and ``trainable="total"``, whose sweeps are those of an ``l_max=0``
+    layer).  ``l_max=0`` is the layer without the argument.
+
+    ``trainable="angular"`` (with ``l_max=1`` or ``2``; htf_at_loss_grad, include/htf_atrain.h) is force matching on the
+    angular conservative forces and implies ``conservative=True``, as ``"total"`` does for ``l_max=0``: under
+    ``tfcompute.attach(..., train=True)`` every step is one ``angular_loss_gradient`` sweep on the step's own list, index and
+    ``total_forces`` output, and one optimizer step; offline, ``angular_loss_gradient(x, labels, index)`` with
+    ``iter_from_trajectory``.  The sweep is ``total_loss_gradient``'s over the wider input, its tangent ``[Gdot | Adot | Qdot]``
+    formed from the moments and their tangents; it is callable on any layer with ``l_max > 0``.  With ``l_max=0`` the value
+    raises and names ``trainable="total"``.
     Limits: ``n_types * K * (1 + l_max) <= 64``, ``H1, H2 <= 64``, at most 256 neighbor slots."""
 
     name = 'descriptor-mlp'
@@ -365,19 +373,22 @@ class DescriptorMLP:
             raise ValueError("DescriptorMLP: l_max must be 0, 1 or 2, not %r" % (l_max,))
         self.l_max = l_max = int(l_max)
         if isinstance(trainable, str):
-            if trainable != "total":
-                raise ValueError("DescriptorMLP: trainable must be False, True or 'total', not %r" % (trainable,))
-            self.trainable, self.conservative = "total", True   # the forces of the total energy, fitted and run alike
+            if trainable not in ("total", "angular"):
+                raise ValueError("DescriptorMLP: trainable must be False, True, 'total' or 'angular', not %r" % (trainable,))
+            if trainable == "angular" and not l_max:
+                raise ValueError("DescriptorMLP: trainable=\"angular\" fits the angular channels and needs l_max = 1 or 2; "
+                                 "trainable=\"total\" fits the conservative forces of an l_max = 0 layer")
+            self.trainable, self.conservative = trainable, True   # the forces of the total energy, fitted and run alike
         else:
             self.trainable, self.conservative = bool(trainable), bool(conservative)
             if self.trainable and self.conservative:
                 raise ValueError("DescriptorMLP: conservative=True cannot go with trainable=True, whose force-matching sweep "
                                  "differentiates the row operator's forces: trainable=\"total\" fits the conservative forces")
         if l_max:
-            if self.trainable:
-                raise NotImplementedError("DescriptorMLP: l_max = %d cannot be trained yet: the force-matching sweep on the angular "
-                                          "conservative forces is the follow-up; fit elsewhere on descriptor() outputs and "
-                                          "load the weights with set_weights / load_weights" % l_max)
+            if self.trainable and self.trainable != "angular":
+                raise NotImplementedError("DescriptorMLP: trainable=%r does not go with l_max = %d: the force-matching sweep on the "
+                                          "angular conservative forces, the follow-up to the angular channels, is "
+                                          "trainable=\"angular\" (angular_loss_gradient)" % (trainable, l_max))
             if not self.conservative:
                 raise ValueError("DescriptorMLP: l_max = %d needs conservative=True: the row operator has no angular form" % l_max)
         if r_cut is not None:
@@ -418,7 +429,7 @@ class DescriptorMLP:
         cfg = {'K': self.K, 'H1': self.H1, 'H2': self.H2, 'low': self.low, 'high': self.high, 'n_types': self.n_types,
                'activation': self.activation}
         if self.trainable:
-            cfg['trainable'] = self.trainable   # (True or "total")
+            cfg['trainable'] = self.trainable   # (True, "total" or "angular")
         if self.r_cut is not None:
             cfg['r_cut'] = self.r_cut
         if self.n_species != 1:
@@ -650,8 +661,25 @@ class DescriptorMLP:
         ``x`` holds the whole system.  Two calls on the same inputs give the same bits.  Callable on any layer, like
         ``total_forces``."""
         if self.l_max:
-            raise NotImplementedError("DescriptorMLP: force matching with l_max = %d is the follow-up to the angular channels"
-                                      % self.l_max)
+            raise NotImplementedError("DescriptorMLP: total_loss_gradient() is the sweep of an l_max = 0 layer; with l_max = %d its "
+                                      "follow-up angular_loss_gradient(x, labels, index) is the force-matching sweep" % self.l_max)
+        return self._conservative_sweep(x, labels, index, types, pred, accum, species)
+
+    def angular_loss_gradient(self, x, labels, index, types=None, pred=None, accum=None, species=None):
+        """``total_loss_gradient`` for a layer with ``l_max = 1`` or ``2`` (htf_at_loss_grad, include/htf_atrain.h): one
+        force-matching sweep on the forces of the total energy with angular channels.  Argument for argument the same: ``accum``
+        [1 + P], or [S, 1 + P] with zero rows for absent species, holds {SSR, d SSR / d theta} per network for the residuals of
+        ``total_forces(x, index, ...)`` against ``labels`` [B, 4]; ``pred`` [B, 4] fp32 is ``total_forces`` at the current
+        weights, evaluated here when not given; the residual is formed in fp32 with torch; a slot whose index is outside
+        ``[0, B)`` has no reverse term.  Two calls on the same inputs give the same bits.  Callable on any layer with
+        ``l_max > 0``, trainable or not; with ``l_max = 0`` it raises."""
+        if not self.l_max:
+            raise ValueError("DescriptorMLP: angular_loss_gradient() is the sweep of the angular channels (l_max = 1 or 2); "
+                             "total_loss_gradient(x, labels, index) is the sweep of this l_max = 0 layer")
+        return self._conservative_sweep(x, labels, index, types, pred, accum, species)
+
+    def _conservative_sweep(self, x, labels, index, types, pred, accum, species):
+        """The sweep on the forces of the total energy for this layer's ``l_max``: htf_ct_loss_grad, or htf_at_loss_grad."""
         B, NN = self._check(x)
         index = self._slot_index(index, x)
         ops._dev(labels, "labels")
@@ -675,11 +703,19 @@ class DescriptorMLP:
         act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
         launches, rows = self._launches(species, x)
         # one scratch buffer for the largest species: the launches run one after the other on the stream
-        scratch = torch.empty(max(1, int(lib.htf_bp_scratch_floats(max([n for _, _, n, _ in launches] or [0]), self.K, self.n_types,
-                                                                   self.H1, self.H2))), dtype=torch.float32, device=x.device)
+        # (sized for D = K n_types (1 + l_max) inputs: P is this layer's)
+        scratch = torch.empty(max(1, int(lib.htf_bp_scratch_floats(max([n for _, _, n, _ in launches] or [0]), self.K,
+                                                                   self.n_types * (1 + self.l_max), self.H1, self.H2))),
+                              dtype=torch.float32, device=x.device)
         present = set()
         for s, d_rows, n_rows, d_w in launches:
             present.add(s)
+            if self.l_max:
+                check(lib.htf_at_loss_grad(x.data_ptr(), ops._dt(x), index.data_ptr(), B, NN, self.K, self.n_types, self.H1, self.H2,
+                                           act, d_w, self.mu.data_ptr(), float(self.gap), rho.data_ptr(),
+                                           accum.data_ptr() + 4 * s * (1 + P), scratch.data_ptr(), d_rows, n_rows,
+                                           float(self.r_cut or 0.0), self.l_max, ops._stream(x)))
+                continue
             check(lib.htf_ct_loss_grad(x.data_ptr(), ops._dt(x), index.data_ptr(), B, NN, self.K, self.n_types, self.H1, self.H2,
                                        act, d_w, self.mu.data_ptr(), float(self.gap), rho.data_ptr(),
                                        accum.data_ptr() + 4 * s * (1 + P), scratch.data_ptr(), d_rows, n_rows,

@@ -435,9 +435,12 @@ class tfcompute:
     @staticmethod
     def _descriptor_sweep(layer, nlist_t, labels, pred, entry, species=None):
         """The layer's sweep for the force definition it trains on: the row operator's (trainable=True), or the forces of the
-        total energy (trainable="total") on the slot index and the types the step's own total_forces call used."""
+        total energy (trainable="total"; with angular channels, trainable="angular") on the slot index and the types the step's
+        own total_forces call used."""
         if layer.trainable == "total":
             return layer.total_loss_gradient(nlist_t, labels, entry["index"], types=entry.get("types"), pred=pred, species=species)
+        if layer.trainable == "angular":
+            return layer.angular_loss_gradient(nlist_t, labels, entry["index"], types=entry.get("types"), pred=pred, species=species)
         return layer.loss_gradient(nlist_t, labels, pred=pred, species=species)
 
     def _train_descriptor_species(self, nlist_t, offset, n, layer, pred, entry):

@@ -1,7 +1,7 @@
 // Angular channels of the descriptor network on its conservative forces (include/htf_angular.h,
 // htf.DescriptorMLP(conservative=True, l_max=1 or 2)): the two sweeps of cforce.hip with neighbor moments.
 //
-// Pass 1 (ang_grad_kernel) is desc_row.h's row through step 4, written out here with the moments: one wave per row, slots in
+// Pass 1 (ang_grad_kernel) is desc_row.h's row through step 4 with the moments in step 2: one wave per row, slots in
 // registers with their direction u, and for every channel c = t K + k ten fixed-order wave sums at most -- G, the vector
 // v = sum w u (l_max >= 1) and the symmetric tensor M = sum w u (outer) u (l_max = 2) -- kept by lane c.  Lane c forms
 // A = |v|^2 and Q = ||M||_F^2, the wave publishes [G | A | Q] (D = Dr (1 + l_max) values) to its exchange line, and the network
@@ -14,7 +14,7 @@
 // float4 per channel for C = 4, five float2 for C = 10 (the table is 16-byte aligned, so those are always aligned) --
 // recomputes the exponentials, and contracts the gathered terms with the slot's own u as they arrive: five accumulators per
 // slot (six with a cutoff), a coefficient along u and a 3-vector.  F_i and the nine entries of W_i follow by the fixed-order
-// wave sums.  No atomics, no scratch; built with -ffp-contract=on like bp.o (csrc/Makefile), so that both instantiations
+// wave sums of desc_pair_force_end (desc_row.h), cf_pair_force_kernel's own end.  No atomics, no scratch; built with -ffp-contract=on like bp.o (csrc/Makefile), so that both instantiations
 // of the row form the moments alike.
 #include "htf_angular.h"
 #include "desc_row.h"
@@ -63,7 +63,8 @@ __device__ __forceinline__ void ang_rows(const typename Vec4<IT>::type *__restri
         const unsigned row = rows ? (unsigned)rows[q] : q;
         const typename Vec4<IT>::type *rp = nlist + (size_t)row * NN;
 
-        // 1. this lane's slots, by the arithmetic of desc_row.h's step 1, and their direction u = (x + 1e-7) / r
+        // 1. this lane's slots, by the arithmetic of desc_row.h's desc_slot and step 1 (written out: through desc_slot the
+        //    l_max = 2 forms took 8 fewer VGPRs and total_forces 0.3 % longer), and their direction u = (x + 1e-7) / r
         float ux[kDescSlots], uy[kDescSlots], uz[kDescSlots], r[kDescSlots], fc[kDescSlots];
         int ty[kDescSlots];
 #pragma unroll
@@ -278,23 +279,16 @@ __global__ __launch_bounds__(256) void ang_force_kernel(const typename Vec4<IT>:
             ty[t] = -1;
             near[t] = false;
             if ((unsigned)t < ns && slot < NN) {
-                const auto v = load_stream(&rp[slot]);
-                x[t] = (float)v.x; y[t] = (float)v.y; z[t] = (float)v.z;
-                const float tx = x[t] + kNormDelta, tyy = y[t] + kNormDelta, tz = z[t] + kNormDelta;
-                const float rr = sqrtf(tx * tx + tyy * tyy + tz * tz);
-                int typ = 0;
-                if (T > 1) {
-                    const IT rw = rint(v.w);
-                    typ = (rw >= (IT)0 && rw < (IT)T) ? (int)rw : -1; // (NaN: -1)
-                }
-                bool live = rr > kRinvDelta;
-                if constexpr (CUT) live = live && rr < rc;
+                const DescSlot s = desc_slot<IT>(&rp[slot], T);
+                x[t] = s.x; y[t] = s.y; z[t] = s.z;
+                bool live = s.rr > kRinvDelta;
+                if constexpr (CUT) live = live && s.rr < rc;
                 if (live) {
                     near[t] = true;
-                    r[t] = rr;
-                    ty[t] = typ;
-                    ux[t] = tx / rr; uy[t] = tyy / rr; uz[t] = tz / rr;
-                    if constexpr (CUT) cutoff_terms(rr, rc, c_fc, fc[t], dfc[t]);
+                    r[t] = s.rr;
+                    ty[t] = s.typ;
+                    ux[t] = s.tx / s.rr; uy[t] = s.tyy / s.rr; uz[t] = s.tz / s.rr;
+                    if constexpr (CUT) cutoff_terms(s.rr, rc, c_fc, fc[t], dfc[t]);
                 }
             }
         }
@@ -400,29 +394,7 @@ __global__ __launch_bounds__(256) void ang_force_kernel(const typename Vec4<IT>:
                 }
             }
         }
-        fx = group_sum<64>(fx);
-        fy = group_sum<64>(fy);
-        fz = group_sum<64>(fz);
-        if constexpr (VIRIAL) {
-#pragma unroll
-            for (int c9 = 0; c9 < 9; ++c9) w[c9] = group_sum<64>(w[c9]);
-        }
-        if (lane == 0) {
-            const float e = energy[row];
-            if (out_f64)
-                ((double4 *)out)[row] = make_double4(fx, fy, fz, e);
-            else
-                ((float4 *)out)[row] = make_float4(fx, fy, fz, e);
-            if constexpr (VIRIAL) {
-#pragma unroll
-                for (int c9 = 0; c9 < 9; ++c9) {
-                    if (out_f64)
-                        ((double *)virial9)[(size_t)row * 9 + c9] = w[c9];
-                    else
-                        ((float *)virial9)[(size_t)row * 9 + c9] = w[c9];
-                }
-            }
-        }
+        desc_pair_force_end<VIRIAL>(lane, row, fx, fy, fz, w, energy, out, out_f64, virial9);
     }
 }
 
@@ -430,10 +402,7 @@ int ang_check(unsigned B, unsigned n_rows, unsigned K, unsigned T, unsigned l_ma
     HTF_REQUIRE(l_max == 1 || l_max == 2, "descriptor network: l_max = %u; the angular entries take 1 or 2 (0: htf_cforce.h)", l_max);
     HTF_REQUIRE(K * T * (1 + l_max) <= (unsigned)kDescMaxD, "descriptor network: K n_types (1 + l_max) = %u * %u * %u inputs; at most %d",
                 K, T, 1 + l_max, kDescMaxD);
-    HTF_REQUIRE(n_rows <= B, "descriptor network: n_rows %u > B %u", n_rows, B);
-    HTF_REQUIRE(r_cut >= 0.0f && r_cut <= 3.402823466e+38f, "descriptor network: r_cut = %g must be finite and positive, or 0 for none",
-                (double)r_cut);
-    return HTF_OK;
+    return desc_check_rows(B, n_rows, r_cut);
 }
 
 size_t ang_lds_forces(unsigned K) { return (((K + 3) & ~3u) + 4 * kAngRegion) * sizeof(float); }

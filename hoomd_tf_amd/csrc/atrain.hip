@@ -7,8 +7,9 @@
 // projection a = d . u of d = rho_i - m rho_j and dperp / r; step 2 forms, per channel and from one exponential per slot, the
 // fixed-order wave sums of w, w' a, w u, vdot and (l_max = 2) M, Mdot -- 8 or 20 of them -- and lane c < Dr turns its channel's
 // into A, Adot, Q, Qdot and writes the three entries it owns of the two input lines.  Steps 3 to 5 -- forward with tangent,
-// reverse, register accumulators, block partials -- are dtrain_rows' statement for statement over D = Dr (1 + l_max) inputs,
-// and the partials are added by bp.hip's dtrain_reduce_kernel, the library's one reduction.  Every term lands on the row that
+// reverse, register accumulators, block partials -- are dtrain_rows' statement for statement over D = Dr (1 + l_max) inputs
+// (called as functions shared with dtrain_rows they cost the l_max = 2 forms 0.9 %: HISTORY.md), the slots are read by
+// desc_row.h's desc_slot, and the partials are added by bp.hip's dtrain_reduce_kernel, the library's one reduction.  Every term lands on the row that
 // reads it: no atomics, no scatter.  Built with -ffp-contract=on like bp.o (csrc/Makefile).
 #include "htf_atrain.h"
 #include "dtrain_row.h"
@@ -81,20 +82,13 @@ __device__ __forceinline__ void at_rows(const typename Vec4<IT>::type *__restric
             fc[t] = dfc[t] = 0.f;
             ty[t] = -1;
             if ((unsigned)t < ns && slot < NN) {
-                const auto v = load_stream(&rp[slot]);
-                const float tx = (float)v.x + kNormDelta, tyy = (float)v.y + kNormDelta, tz = (float)v.z + kNormDelta;
-                const float rr = sqrtf(tx * tx + tyy * tyy + tz * tz);
-                int typ = 0;
-                if (T > 1) {
-                    const IT rw = rint(v.w);
-                    typ = (rw >= (IT)0 && rw < (IT)T) ? (int)rw : -1; // (NaN: -1)
-                }
-                bool live = rr > kRinvDelta && typ >= 0;
-                if constexpr (CUT) live = live && rr < rc;
+                const DescSlot s = desc_slot<IT>(&rp[slot], T);
+                bool live = s.rr > kRinvDelta && s.typ >= 0;
+                if constexpr (CUT) live = live && s.rr < rc;
                 if (live) {
-                    r[t] = rr;
-                    ty[t] = typ;
-                    ux[t] = tx / rr; uy[t] = tyy / rr; uz[t] = tz / rr;
+                    r[t] = s.rr;
+                    ty[t] = s.typ;
+                    ux[t] = s.tx / s.rr; uy[t] = s.tyy / s.rr; uz[t] = s.tz / s.rr;
                     float dx = rx, dy = ry, dz = rz;
                     const int j = index[(size_t)row * NN + slot];
                     if ((unsigned)j < B) {   // (a negative index is above B as unsigned)
@@ -103,8 +97,8 @@ __device__ __forceinline__ void at_rows(const typename Vec4<IT>::type *__restric
                     }
                     const float aa = dx * ux[t] + dy * uy[t] + dz * uz[t];
                     a[t] = aa;
-                    px[t] = (dx - aa * ux[t]) / rr; py[t] = (dy - aa * uy[t]) / rr; pz[t] = (dz - aa * uz[t]) / rr;
-                    if constexpr (CUT) cutoff_terms(rr, rc, c_fc, fc[t], dfc[t]);
+                    px[t] = (dx - aa * ux[t]) / s.rr; py[t] = (dy - aa * uy[t]) / s.rr; pz[t] = (dz - aa * uz[t]) / s.rr;
+                    if constexpr (CUT) cutoff_terms(s.rr, rc, c_fc, fc[t], dfc[t]);
                 }
             }
         }
@@ -289,10 +283,7 @@ int at_check(unsigned B, unsigned n_rows, unsigned K, unsigned T, unsigned l_max
     HTF_REQUIRE(l_max == 1 || l_max == 2, "descriptor network: l_max = %u; the angular sweep takes 1 or 2 (0: htf_ctrain.h)", l_max);
     HTF_REQUIRE(K * T * (1 + l_max) <= (unsigned)kDescMaxD, "descriptor network: K n_types (1 + l_max) = %u * %u * %u inputs; at most %d",
                 K, T, 1 + l_max, kDescMaxD);
-    HTF_REQUIRE(n_rows <= B, "descriptor network: n_rows %u > B %u", n_rows, B);
-    HTF_REQUIRE(r_cut >= 0.0f && r_cut <= 3.402823466e+38f, "descriptor network: r_cut = %g must be finite and positive, or 0 for none",
-                (double)r_cut);
-    return HTF_OK;
+    return desc_check_rows(B, n_rows, r_cut);
 }
 
 } // namespace

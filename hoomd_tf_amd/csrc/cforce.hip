@@ -4,11 +4,12 @@
 // Pass 1 is desc_row.h's row through step 4 (its GRAD switch): the network forward and backward of every listed row, one
 // wave per row, g_i = dE_i/dG_i written from lanes < D and E_i from lane 0.  One launch per species, as htf_bp_forces.
 //
-// Pass 2 is one launch over all rows, one wave per row, slots in registers exactly as the row kernel loads them
+// Pass 2 is one launch over all rows, one wave per row, slots in registers read by the row kernel's own desc_slot
 // (the same r, fc, fc').  The wave stages its own g_i in its LDS line; each lane gathers, per slot, the
 // K floats g[j][t_i K ..] of the slot's particle j -- one 4 K-byte run per lane from a table of B D floats, as float4 where K is
 // a multiple of 4 (every run is then 16-byte aligned) -- and recomputes the exponentials as step 5 of the row kernel does.
-// phi, F_i and W_i follow by the fixed-order wave sums.  No atomics, no scratch: a row's bits depend on its slots, its
+// phi, F_i and W_i follow by the fixed-order wave sums and the store of desc_pair_force_end (desc_row.h), which
+// angular.hip's pass 2 ends in too.  No atomics, no scratch: a row's bits depend on its slots, its
 // indices and the gathered rows of g alone.  Built with -ffp-contract=on like bp.o (csrc/Makefile), so that pass 1 forms
 // the energy bit for bit as the force kernel does.
 #include "htf_cforce.h"
@@ -51,7 +52,7 @@ __global__ __launch_bounds__(256) void cf_pair_force_kernel(const typename Vec4<
         const typename Vec4<IT>::type *rp = nlist + (size_t)row * NN;
         const int *ip = index + (size_t)row * NN;
 
-        // 1. this lane's slots, by the arithmetic of desc_row.h's step 1 (the same r, fc and fc'), with one difference: a slot
+        // 1. this lane's slots, read by desc_row.h's desc_slot (the same r, fc and fc'), with a keep rule of its own: a slot
         //    is kept (near) on its distance alone, and a neighbor type outside [0, T) only empties its forward term (ty = -1) --
         //    the neighbor's own energy still depends on this row's particle
         float x[kDescSlots], y[kDescSlots], z[kDescSlots], r[kDescSlots];
@@ -67,22 +68,15 @@ __global__ __launch_bounds__(256) void cf_pair_force_kernel(const typename Vec4<
             ty[t] = -1;
             near[t] = false;
             if ((unsigned)t < ns && slot < NN) {
-                const auto v = load_stream(&rp[slot]);
-                x[t] = (float)v.x; y[t] = (float)v.y; z[t] = (float)v.z;
-                const float tx = x[t] + kNormDelta, tyy = y[t] + kNormDelta, tz = z[t] + kNormDelta;
-                const float rr = sqrtf(tx * tx + tyy * tyy + tz * tz);
-                int typ = 0;
-                if (T > 1) {
-                    const IT rw = rint(v.w);
-                    typ = (rw >= (IT)0 && rw < (IT)T) ? (int)rw : -1; // (NaN: -1)
-                }
-                bool live = rr > kRinvDelta;
-                if constexpr (CUT) live = live && rr < rc;
+                const DescSlot s = desc_slot<IT>(&rp[slot], T);
+                x[t] = s.x; y[t] = s.y; z[t] = s.z;
+                bool live = s.rr > kRinvDelta;
+                if constexpr (CUT) live = live && s.rr < rc;
                 if (live) {
                     near[t] = true;
-                    r[t] = rr;
-                    ty[t] = typ;
-                    if constexpr (CUT) cutoff_terms(rr, rc, c_fc, fc[t], dfc[t]);
+                    r[t] = s.rr;
+                    ty[t] = s.typ;
+                    if constexpr (CUT) cutoff_terms(s.rr, rc, c_fc, fc[t], dfc[t]);
                 }
             }
         }
@@ -164,37 +158,8 @@ __global__ __launch_bounds__(256) void cf_pair_force_kernel(const typename Vec4<
                 }
             }
         }
-        fx = group_sum<64>(fx);
-        fy = group_sum<64>(fy);
-        fz = group_sum<64>(fz);
-        if constexpr (VIRIAL) {
-#pragma unroll
-            for (int c9 = 0; c9 < 9; ++c9) w[c9] = group_sum<64>(w[c9]);
-        }
-        if (lane == 0) {
-            const float e = energy[row];
-            if (out_f64)
-                ((double4 *)out)[row] = make_double4(fx, fy, fz, e);
-            else
-                ((float4 *)out)[row] = make_float4(fx, fy, fz, e);
-            if constexpr (VIRIAL) {
-#pragma unroll
-                for (int c9 = 0; c9 < 9; ++c9) {
-                    if (out_f64)
-                        ((double *)virial9)[(size_t)row * 9 + c9] = w[c9];
-                    else
-                        ((float *)virial9)[(size_t)row * 9 + c9] = w[c9];
-                }
-            }
-        }
+        desc_pair_force_end<VIRIAL>(lane, row, fx, fy, fz, w, energy, out, out_f64, virial9);
     }
-}
-
-int cf_check(unsigned B, unsigned n_rows, float r_cut) {
-    HTF_REQUIRE(n_rows <= B, "descriptor network: n_rows %u > B %u", n_rows, B);
-    HTF_REQUIRE(r_cut >= 0.0f && r_cut <= 3.402823466e+38f, "descriptor network: r_cut = %g must be finite and positive, or 0 for none",
-                (double)r_cut);
-    return HTF_OK;
 }
 
 } // namespace
@@ -207,7 +172,7 @@ extern "C" int htf_cf_grad(const void *d_nlist, int nlist_dtype, unsigned B, uns
     int rc = desc_check(d_nlist, nlist_dtype, B, NN, K, n_types, d_mu, gap, d_g, HTF_F32);
     if (rc != HTF_OK) return rc;
     if ((rc = desc_check_network(d_weights, H1, H2, activation)) != HTF_OK) return rc;
-    if ((rc = cf_check(B, n_rows, r_cut)) != HTF_OK) return rc;
+    if ((rc = desc_check_rows(B, n_rows, r_cut)) != HTF_OK) return rc;
     HTF_REQUIRE(B == 0 || d_energy, "descriptor network: null pointer");
     if (n_rows == 0) return HTF_OK;
     const size_t lds = desc_lds_forces(K, n_types, H1, H2);
@@ -240,7 +205,7 @@ extern "C" int htf_cf_forces(const void *d_nlist, int nlist_dtype, const int *d_
     using namespace htf;
     int rc = desc_check(d_nlist, nlist_dtype, B, NN, K, n_types, d_mu, gap, d_force, force_dtype);
     if (rc != HTF_OK) return rc;
-    if ((rc = cf_check(B, B, r_cut)) != HTF_OK) return rc;
+    if ((rc = desc_check_rows(B, B, r_cut)) != HTF_OK) return rc;
     HTF_REQUIRE(B == 0 || (d_index && d_g && d_energy), "descriptor network: null pointer");
     HTF_REQUIRE(B == 0 || n_types == 1 || d_types, "descriptor network: n_types = %u needs the rows' own types", n_types);
     if (B == 0) return HTF_OK;

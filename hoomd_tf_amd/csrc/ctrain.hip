@@ -21,13 +21,6 @@ __global__ __launch_bounds__(256, 1) void ct_sweep_kernel(const typename Vec4<IT
     dtrain_rows<TANH, CUT, LIST, IT, true>(nlist, rows, n, NN, weights, mu, K, T, H1, H2, gap, rc, nullptr, 0, rho, partials, index, B);
 }
 
-int ct_check(unsigned B, unsigned n_rows, float r_cut) {
-    HTF_REQUIRE(n_rows <= B, "descriptor network: n_rows %u > B %u", n_rows, B);
-    HTF_REQUIRE(r_cut >= 0.0f && r_cut <= 3.402823466e+38f, "descriptor network: r_cut = %g must be finite and positive, or 0 for none",
-                (double)r_cut);
-    return HTF_OK;
-}
-
 } // namespace
 } // namespace htf
 
@@ -41,7 +34,7 @@ extern "C" int htf_ct_loss_grad(const void *d_nlist, int nlist_dtype, const int 
                                d_accum, d_scratch);
     if (rc != HTF_OK) return rc;
     HTF_REQUIRE(B == 0 || d_index, "descriptor network: null pointer");
-    if ((rc = ct_check(B, n_rows, r_cut)) != HTF_OK) return rc;
+    if ((rc = desc_check_rows(B, n_rows, r_cut)) != HTF_OK) return rc;
     if (!d_accum) return HTF_OK;   // (B = 0 and nothing to zero-fill: no launch)
     const unsigned n = 1u + dtrain_params(K * n_types, H1, H2);
     const unsigned grid = dtrain_grid(n_rows);   // (0 for no rows: the reduction alone then writes zeros)

@@ -56,6 +56,59 @@ __device__ __forceinline__ void line_publish(float *line, unsigned lane, float v
 // floats of the weights in LDS: W1 [D][H1 + 1] | b1 | W2 [H1][H2 + 1] | b2 | W3 | b3
 __host__ __device__ inline int desc_lds_weights(int D, int H1, int H2) { return D * (H1 + 1) + H1 + H1 * (H2 + 1) + H2 + H2 + 1; }
 
+// One slot of a row as every kernel of the family reads it: 16 B (32 B from an fp64 tensor), once.  Which slots a kernel
+// keeps is its own rule, written with these fields where the slot is read.  (Returned by value, not filled through a pointer:
+// the fields are then plain values before anything is inlined, as the pasted statements' locals were.)
+struct DescSlot {
+    float x, y, z;      // the raw pair vector (the virial's)
+    float tx, tyy, tz;  // shifted by 1e-7 as the graph shifts it (tyy: ty[] is the slots' types wherever a slot is read)
+    float rr;           // |t|
+    int typ;            // the neighbor's type in [0, T), or -1
+};
+template <typename IT>
+__device__ __forceinline__ DescSlot desc_slot(const typename Vec4<IT>::type *p, int T) {
+    const auto v = load_stream(p);
+    const float x = (float)v.x, y = (float)v.y, z = (float)v.z;
+    const float tx = x + kNormDelta, tyy = y + kNormDelta, tz = z + kNormDelta;
+    const float rr = sqrtf(tx * tx + tyy * tyy + tz * tz);
+    int typ = 0;
+    if (T > 1) {
+        const IT rw = rint(v.w);
+        typ = (rw >= (IT)0 && rw < (IT)T) ? (int)rw : -1; // (NaN: -1)
+    }
+    return {x, y, z, tx, tyy, tz, rr, typ};
+}
+
+// The end of a pass-2 row of the conservative forces (cforce.hip, angular.hip): the fixed-order wave sums of the lanes' F and W
+// terms, then lane 0 stores them, with the row's energy from pass 1, in either output dtype.
+template <bool VIRIAL>
+__device__ __forceinline__ void desc_pair_force_end(unsigned lane, unsigned row, float fx, float fy, float fz, float (&w)[9],
+                                                    const float *__restrict__ energy, void *out, int out_f64, void *virial9) {
+    fx = group_sum<64>(fx);
+    fy = group_sum<64>(fy);
+    fz = group_sum<64>(fz);
+    if constexpr (VIRIAL) {
+#pragma unroll
+        for (int c9 = 0; c9 < 9; ++c9) w[c9] = group_sum<64>(w[c9]);
+    }
+    if (lane == 0) {
+        const float e = energy[row];
+        if (out_f64)
+            ((double4 *)out)[row] = make_double4(fx, fy, fz, e);
+        else
+            ((float4 *)out)[row] = make_float4(fx, fy, fz, e);
+        if constexpr (VIRIAL) {
+#pragma unroll
+            for (int c9 = 0; c9 < 9; ++c9) {
+                if (out_f64)
+                    ((double *)virial9)[(size_t)row * 9 + c9] = w[c9];
+                else
+                    ((float *)virial9)[(size_t)row * 9 + c9] = w[c9];
+            }
+        }
+    }
+}
+
 // FORCES = false: G alone, written to out [B][D].  FORCES = true: out [B][4] (f, E) and, with VIRIAL, virial9 [B][9].
 // n work items: rows 0 .. n - 1, or rows[0 .. n - 1] with LIST (rows is then not null).
 // GRAD (with FORCES, pass 1 of the conservative forces, cforce.hip): the row ends after step 4 -- out [B][D] fp32 receives
@@ -109,21 +162,14 @@ __device__ __forceinline__ void desc_rows(const typename Vec4<IT>::type *__restr
             fc[t] = dfc[t] = 0.f;
             ty[t] = -1;
             if ((unsigned)t < ns && slot < NN) {
-                const auto v = load_stream(&rp[slot]);
-                x[t] = (float)v.x; y[t] = (float)v.y; z[t] = (float)v.z;
-                const float tx = x[t] + kNormDelta, tyy = y[t] + kNormDelta, tz = z[t] + kNormDelta;
-                const float rr = sqrtf(tx * tx + tyy * tyy + tz * tz);
-                int typ = 0;
-                if (T > 1) {
-                    const IT rw = rint(v.w);
-                    typ = (rw >= (IT)0 && rw < (IT)T) ? (int)rw : -1; // (NaN: -1)
-                }
-                bool live = rr > kRinvDelta && typ >= 0;
-                if constexpr (CUT) live = live && rr < rc;
+                const DescSlot s = desc_slot<IT>(&rp[slot], T);
+                x[t] = s.x; y[t] = s.y; z[t] = s.z;
+                bool live = s.rr > kRinvDelta && s.typ >= 0;
+                if constexpr (CUT) live = live && s.rr < rc;
                 if (live) {
-                    r[t] = rr;
-                    ty[t] = typ;
-                    if constexpr (CUT) cutoff_terms(rr, rc, c_fc, fc[t], dfc[t]);
+                    r[t] = s.rr;
+                    ty[t] = s.typ;
+                    if constexpr (CUT) cutoff_terms(s.rr, rc, c_fc, fc[t], dfc[t]);
                 }
             }
         }
@@ -282,6 +328,14 @@ inline int desc_check_network(const float *weights, unsigned H1, unsigned H2, in
     HTF_REQUIRE(H1 >= 1 && H1 <= (unsigned)kDescMaxH && H2 >= 1 && H2 <= (unsigned)kDescMaxH,
                 "descriptor network: hidden widths %u, %u outside [1, %d]", H1, H2, kDescMaxH);
     HTF_REQUIRE(activation == HTF_ACT_LINEAR || activation == HTF_ACT_TANH, "descriptor network: unknown activation %d", activation);
+    return HTF_OK;
+}
+
+// a row list and a cutoff as every entry that takes them checks them
+inline int desc_check_rows(unsigned B, unsigned n_rows, float r_cut) {
+    HTF_REQUIRE(n_rows <= B, "descriptor network: n_rows %u > B %u", n_rows, B);
+    HTF_REQUIRE(r_cut >= 0.0f && r_cut <= 3.402823466e+38f, "descriptor network: r_cut = %g must be finite and positive, or 0 for none",
+                (double)r_cut);
     return HTF_OK;
 }
 

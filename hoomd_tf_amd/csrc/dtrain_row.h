@@ -9,7 +9,7 @@
 //   dQ/dW2 = h1 zb2^T + hd1 zdb2^T, dQ/db2 = zb2;  hb1 = W2 zb2, hdb1 = W2 zdb2
 //   zb1 = hb1 s1 + hdb1 c1 zd1, zdb1 = hdb1 s1;  dQ/dW1 = G zb1^T + Gdot zdb1^T, dQ/db1 = zb1
 //
-// Layout: that of desc_row.h.  One wave64 per row in a grid-stride loop, up to four slots of the row per lane in registers,
+// Layout: that of desc_row.h, whose slot reader (desc_slot) the row uses.  One wave64 per row in a grid-stride loop, up to four slots of the row per lane in registers,
 // channel t*K + k in lane t*K + k, one hidden unit per lane, activations exchanged through wave-private LDS lines, the
 // weights staged in LDS once per block with odd row strides.  G and Gdot are formed together from the same exponentials.
 // The weight gradient is kept as outer-product accumulators in registers for the whole kernel: lane a owns column a of dW1
@@ -140,19 +140,12 @@ __device__ __forceinline__ void dtrain_rows(const typename Vec4<IT>::type *__res
             fc[t] = dfc[t] = 0.f;
             ty[t] = -1;
             if ((unsigned)t < ns && slot < NN) {
-                const auto v = load_stream(&rp[slot]);
-                const float tx = (float)v.x + kNormDelta, tyy = (float)v.y + kNormDelta, tz = (float)v.z + kNormDelta;
-                const float rr = sqrtf(tx * tx + tyy * tyy + tz * tz);
-                int typ = 0;
-                if (T > 1) {
-                    const IT rw = rint(v.w);
-                    typ = (rw >= (IT)0 && rw < (IT)T) ? (int)rw : -1; // (NaN: -1)
-                }
-                bool live = rr > kRinvDelta && typ >= 0;
-                if constexpr (CUT) live = live && rr < rc;
+                const DescSlot s = desc_slot<IT>(&rp[slot], T);
+                bool live = s.rr > kRinvDelta && s.typ >= 0;
+                if constexpr (CUT) live = live && s.rr < rc;
                 if (live) {
-                    r[t] = rr;
-                    ty[t] = typ;
+                    r[t] = s.rr;
+                    ty[t] = s.typ;
                     if constexpr (TOTAL) {
                         float ax = rx, ay = ry, az = rz;
                         const int j = index[(size_t)row * NN + slot];
@@ -160,11 +153,11 @@ __device__ __forceinline__ void dtrain_rows(const typename Vec4<IT>::type *__res
                             const float4 rj = pred[j];
                             ax -= rj.x; ay -= rj.y; az -= rj.z;
                         }
-                        a[t] = (ax * tx + ay * tyy + az * tz) / rr;
+                        a[t] = (ax * s.tx + ay * s.tyy + az * s.tz) / s.rr;
                     } else {
-                        a[t] = 2.0f * (rx * tx + ry * tyy + rz * tz) / rr;
+                        a[t] = 2.0f * (rx * s.tx + ry * s.tyy + rz * s.tz) / s.rr;
                     }
-                    if constexpr (CUT) cutoff_terms(rr, rc, c_fc, fc[t], dfc[t]);
+                    if constexpr (CUT) cutoff_terms(s.rr, rc, c_fc, fc[t], dfc[t]);
                 }
             }
         }

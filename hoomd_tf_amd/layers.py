@@ -616,12 +616,29 @@ class DescriptorMLP:
         ``s``'s rows, zeros when it has none; each row steps its own slice of ``w``."""
         self._no_angular("loss_gradient")
         B, NN = self._check(x)
+        pred, accum, launches, rows, scratch = self._sweep_buffers(x, labels, pred, accum, species,
+                                                                   lambda: self.forces(x, species=species))
+        P = self.P
+        act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
+        for s, d_rows, n_rows, d_w in launches:
+            check(lib.htf_bp_loss_grad(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, d_w,
+                                       self.mu.data_ptr(), float(self.gap), labels.data_ptr(), ops._dt(labels), pred.data_ptr(),
+                                       accum.data_ptr() + 4 * s * (1 + P), scratch.data_ptr(), d_rows, n_rows,
+                                       float(self.r_cut or 0.0), ops._stream(x)))
+        return accum
+
+    def _sweep_buffers(self, x, labels, pred, accum, species, evaluate):
+        """What the force-matching sweeps share ahead of their C calls: the checks of ``labels``, of ``pred`` (``evaluate()``,
+        in fp32, when not given) and of ``accum`` (made here when not given), the launches, one scratch buffer, and zeros in the
+        rows of ``accum`` whose species is absent.  Returns (pred, accum, launches, rows, scratch); ``rows`` is what
+        ``_launches`` asks its caller to keep."""
+        B = int(x.shape[0])
         ops._dev(labels, "labels")
         ops._dt(labels)
         if tuple(labels.shape) != (B, 4) or labels.device != x.device:
             raise ValueError("DescriptorMLP: labels must be [%d, 4] on %s, got %s on %s" % (B, x.device, tuple(labels.shape), labels.device))
         if pred is None:
-            pred = self.forces(x, species=species)
+            pred = evaluate()
             if pred.dtype != torch.float32:
                 pred = pred.to(torch.float32)
         ops._dev(pred, "pred", torch.float32)
@@ -633,23 +650,17 @@ class DescriptorMLP:
         ops._dev(accum, "accum", torch.float32)
         if accum.numel() != S * (1 + P) or accum.device != x.device:
             raise ValueError("DescriptorMLP: accum must hold %d floats on %s" % (S * (1 + P), x.device))
-        act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
         launches, rows = self._launches(species, x)
         # one scratch buffer for the largest species: the launches run one after the other on the stream
-        scratch = torch.empty(max(1, int(lib.htf_bp_scratch_floats(max([n for _, _, n, _ in launches] or [0]), self.K, self.n_types,
-                                                                   self.H1, self.H2))), dtype=torch.float32, device=x.device)
-        present = set()
-        for s, d_rows, n_rows, d_w in launches:
-            present.add(s)
-            check(lib.htf_bp_loss_grad(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, d_w,
-                                       self.mu.data_ptr(), float(self.gap), labels.data_ptr(), ops._dt(labels), pred.data_ptr(),
-                                       accum.data_ptr() + 4 * s * (1 + P), scratch.data_ptr(), d_rows, n_rows,
-                                       float(self.r_cut or 0.0), ops._stream(x)))
-        if S > 1:
-            for s in range(S):
-                if s not in present:
-                    accum.view(S, 1 + P)[s].zero_()
-        return accum
+        # (sized for D = K n_types (1 + l_max) inputs: P is this layer's)
+        scratch = torch.empty(max(1, int(lib.htf_bp_scratch_floats(max([n for _, _, n, _ in launches] or [0]), self.K,
+                                                                   self.n_types * (1 + self.l_max), self.H1, self.H2))),
+                              dtype=torch.float32, device=x.device)
+        present = {s for s, _, _, _ in launches}   # (every other row of accum is written by its species' launch)
+        for s in range(S):
+            if s not in present:
+                accum.view(S, 1 + P)[s].zero_()
+        return pred, accum, launches, rows, scratch
 
     def total_loss_gradient(self, x, labels, index, types=None, pred=None, accum=None, species=None):
         """One force-matching sweep on the forces of the total energy (htf_ct_loss_grad, include/htf_ctrain.h): ``accum`` as
@@ -682,34 +693,12 @@ class DescriptorMLP:
         """The sweep on the forces of the total energy for this layer's ``l_max``: htf_ct_loss_grad, or htf_at_loss_grad."""
         B, NN = self._check(x)
         index = self._slot_index(index, x)
-        ops._dev(labels, "labels")
-        ops._dt(labels)
-        if tuple(labels.shape) != (B, 4) or labels.device != x.device:
-            raise ValueError("DescriptorMLP: labels must be [%d, 4] on %s, got %s on %s" % (B, x.device, tuple(labels.shape), labels.device))
-        if pred is None:
-            pred = self.total_forces(x, index, types=types, species=species)
-            if pred.dtype != torch.float32:
-                pred = pred.to(torch.float32)
-        ops._dev(pred, "pred", torch.float32)
-        if tuple(pred.shape) != (B, 4) or pred.device != x.device:
-            raise ValueError("DescriptorMLP: pred must be [%d, 4] on %s, got %s on %s" % (B, x.device, tuple(pred.shape), pred.device))
+        pred, accum, launches, rows, scratch = self._sweep_buffers(
+            x, labels, pred, accum, species, lambda: self.total_forces(x, index, types=types, species=species))
         rho = (pred.detach() - labels.detach().to(torch.float32)).contiguous()
-        S, P = self.n_species, self.P
-        if accum is None:
-            accum = torch.empty((S, 1 + P) if S > 1 else (1 + P,), dtype=torch.float32, device=x.device)
-        ops._dev(accum, "accum", torch.float32)
-        if accum.numel() != S * (1 + P) or accum.device != x.device:
-            raise ValueError("DescriptorMLP: accum must hold %d floats on %s" % (S * (1 + P), x.device))
+        P = self.P
         act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
-        launches, rows = self._launches(species, x)
-        # one scratch buffer for the largest species: the launches run one after the other on the stream
-        # (sized for D = K n_types (1 + l_max) inputs: P is this layer's)
-        scratch = torch.empty(max(1, int(lib.htf_bp_scratch_floats(max([n for _, _, n, _ in launches] or [0]), self.K,
-                                                                   self.n_types * (1 + self.l_max), self.H1, self.H2))),
-                              dtype=torch.float32, device=x.device)
-        present = set()
         for s, d_rows, n_rows, d_w in launches:
-            present.add(s)
             if self.l_max:
                 check(lib.htf_at_loss_grad(x.data_ptr(), ops._dt(x), index.data_ptr(), B, NN, self.K, self.n_types, self.H1, self.H2,
                                            act, d_w, self.mu.data_ptr(), float(self.gap), rho.data_ptr(),
@@ -720,10 +709,6 @@ class DescriptorMLP:
                                        act, d_w, self.mu.data_ptr(), float(self.gap), rho.data_ptr(),
                                        accum.data_ptr() + 4 * s * (1 + P), scratch.data_ptr(), d_rows, n_rows,
                                        float(self.r_cut or 0.0), ops._stream(x)))
-        if S > 1:
-            for s in range(S):
-                if s not in present:
-                    accum.view(S, 1 + P)[s].zero_()
         return accum
 
     def descriptor(self, nlist):

@@ -10,7 +10,8 @@ network ``DescriptorMLP``, its force-matching sweep, smooth cutoff and one netwo
 ``DescriptorMLP(conservative=True)``, and the slot-aligned index tensor ``Nlist.index`` they read: include/htf_cforce.h; force
 matching on those forces, ``DescriptorMLP(trainable="total")`` and ``total_loss_gradient``: include/htf_ctrain.h; angular channels on the conservative
 forces, ``DescriptorMLP(conservative=True, l_max=1 or 2)``: include/htf_angular.h; force matching on those, ``DescriptorMLP(l_max=1 or 2,
-trainable="angular")`` and ``angular_loss_gradient``: include/htf_atrain.h).
+trainable="angular")`` and ``angular_loss_gradient``: include/htf_atrain.h; the same forces and sweeps on one slab domain's
+rows, with the ghost particles' table rows from their owners: include/htf_cghost.h).
 The offline path ``iter_from_trajectory`` / ``ArrayTrajectory`` runs a
 ``SimModel`` over stored frames.
 """

@@ -303,9 +303,19 @@ AT_PROTOTYPES = {
     "htf_at_loss_grad": (_i, [_vp, _i, _vp, _u, _u, _u, _u, _u, _u, _i, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _u, C.c_float, _u, _vp]),
 }
 
+# the same forces and sweeps on one domain's rows, with the ghosts' table rows (include/htf_cghost.h; DescriptorMLP's n_ghost,
+# domain.SlabDomain.halo_rows): each is its twin's prototype with ``unsigned n_table`` before the stream
+CGHOST_PROTOTYPES = {
+    "htf_cf_forces_ghost": (_i, CF_PROTOTYPES["htf_cf_forces"][1][:-1] + [_u, _vp]),
+    "htf_ang_forces_ghost": (_i, ANG_PROTOTYPES["htf_ang_forces"][1][:-1] + [_u, _vp]),
+    "htf_ct_loss_grad_ghost": (_i, CT_PROTOTYPES["htf_ct_loss_grad"][1][:-1] + [_u, _vp]),
+    "htf_at_loss_grad_ghost": (_i, AT_PROTOTYPES["htf_at_loss_grad"][1][:-1] + [_u, _vp]),
+}
+
 # every table above: what the ctypes and the pybind11 binding both declare
 ALL_PROTOTYPES = tuple((name, proto) for table in (PROTOTYPES, STANDIN_PROTOTYPES, STEP_CHECK_PROTOTYPES, CG_PROTOTYPES, GEOM_PROTOTYPES, NLIST_PROTOTYPES,
-                                                   BP_PROTOTYPES, CF_PROTOTYPES, CT_PROTOTYPES, ANG_PROTOTYPES, AT_PROTOTYPES) for name, proto in table.items())
+                                                   BP_PROTOTYPES, CF_PROTOTYPES, CT_PROTOTYPES, ANG_PROTOTYPES, AT_PROTOTYPES, CGHOST_PROTOTYPES)
+                       for name, proto in table.items())
 
 
 ABI_VERSION = 5  # include/htf_amd.h HTF_AMD_ABI_VERSION: the struct layouts the ctypes Structures of this file mirror

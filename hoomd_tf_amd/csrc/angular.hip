@@ -17,6 +17,7 @@
 // wave sums of desc_pair_force_end (desc_row.h), cf_pair_force_kernel's own end.  No atomics, no scratch; built with -ffp-contract=on like bp.o (csrc/Makefile), so that both instantiations
 // of the row form the moments alike.
 #include "htf_angular.h"
+#include "htf_cghost.h"
 #include "desc_row.h"
 
 namespace htf {
@@ -237,9 +238,10 @@ __global__ __launch_bounds__(256) void ang_desc_kernel(const typename Vec4<IT>::
     ang_rows<false, false, CUT, LMAX, IT>(nlist, nullptr, n, NN, nullptr, mu, K, T, 0, 0, gap, rc, nullptr, nullptr, out, out_f64);
 }
 
+// n_table >= B: the rows of the table (include/htf_cghost.h); rows [B, n_table) are ghosts' rows, read through a slot's index only
 template <bool VIRIAL, bool CUT, int LMAX, typename IT>
 __global__ __launch_bounds__(256) void ang_force_kernel(const typename Vec4<IT>::type *__restrict__ nlist, const int *__restrict__ index,
-                                                        const float *__restrict__ types, unsigned B, unsigned NN,
+                                                        const float *__restrict__ types, unsigned B, unsigned n_table, unsigned NN,
                                                         const float *__restrict__ mu, int K, int T, float gap, float rc,
                                                         const float *__restrict__ table, const float *__restrict__ energy,
                                                         void *__restrict__ out, int out_f64, void *__restrict__ virial9) {
@@ -258,6 +260,9 @@ __global__ __launch_bounds__(256) void ang_force_kernel(const typename Vec4<IT>:
     const unsigned lane = threadIdx.x & 63u;
     const unsigned ns = (NN + 63u) >> 6;            // slots per lane in use (wave-uniform)
     const unsigned stride = gridDim.x * (blockDim.x >> 6);
+    // the index bound in a vector register: as one more scalar held across the row loop it spilled two SGPRs in three forms
+    unsigned n_index = n_table;
+    asm volatile("" : "+v"(n_index));
 
     for (unsigned row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); row < B; row += stride) { // wave-uniform
         const typename Vec4<IT>::type *rp = nlist + (size_t)row * NN;
@@ -293,7 +298,7 @@ __global__ __launch_bounds__(256) void ang_force_kernel(const typename Vec4<IT>:
             }
         }
 
-        // 2. where each slot's reverse terms live: h[j][t_i K ..], or nowhere (index outside [0, B), own type out of range)
+        // 2. where each slot's reverse terms live: h[j][t_i K ..], or nowhere (index outside [0, n_table), own type out of range)
         int ti = 0;
         if (T > 1) {
             const float tw = rintf(types[row]);
@@ -305,7 +310,7 @@ __global__ __launch_bounds__(256) void ang_force_kernel(const typename Vec4<IT>:
             hj[t] = nullptr;
             if ((unsigned)t < ns && near[t] && ti >= 0) {   // (a kept slot: t * 64 + lane < NN)
                 const int j = ip[t * 64 + lane];
-                if ((unsigned)j < B) hj[t] = table + ((size_t)j * Dr + ti * K) * C;
+                if ((unsigned)j < n_index) hj[t] = table + ((size_t)j * Dr + ti * K) * C;
             }
         }
         __builtin_amdgcn_wave_barrier();   // (the previous row's region has been read by every lane)
@@ -445,10 +450,12 @@ extern "C" int htf_ang_grad(const void *d_nlist, int nlist_dtype, unsigned B, un
     return check_launch("ang_grad_kernel");
 }
 
-extern "C" int htf_ang_forces(const void *d_nlist, int nlist_dtype, const int *d_index, const float *d_types, unsigned B, unsigned NN,
-                              unsigned K, unsigned n_types, const float *d_mu, float gap, const float *d_table, const float *d_energy,
-                              void *d_force, int force_dtype, void *d_virial9, float r_cut, unsigned l_max, htf_stream stream) {
+extern "C" int htf_ang_forces_ghost(const void *d_nlist, int nlist_dtype, const int *d_index, const float *d_types, unsigned B,
+                                    unsigned NN, unsigned K, unsigned n_types, const float *d_mu, float gap, const float *d_table,
+                                    const float *d_energy, void *d_force, int force_dtype, void *d_virial9, float r_cut,
+                                    unsigned l_max, unsigned n_table, htf_stream stream) {
     using namespace htf;
+    HTF_REQUIRE(n_table >= B, "descriptor network: n_table %u < B %u", n_table, B);
     int rc = desc_check(d_nlist, nlist_dtype, B, NN, K, n_types, d_mu, gap, d_force, force_dtype);
     if (rc != HTF_OK) return rc;
     if ((rc = ang_check(B, B, K, n_types, l_max, r_cut)) != HTF_OK) return rc;
@@ -461,7 +468,7 @@ extern "C" int htf_ang_forces(const void *d_nlist, int nlist_dtype, const int *d
     const hipStream_t s = (hipStream_t)stream;
 #define HTF_AF(VIR, CUT, LM, T, V4)                                                                                                  \
     hipLaunchKernelGGL((ang_force_kernel<VIR, CUT, LM, T>), dim3(desc_grid(B)), dim3(256), lds, s, (const V4 *)d_nlist, d_index,       \
-                       d_types, B, NN, d_mu, (int)K, (int)n_types, gap, r_cut, d_table, d_energy, d_force, out_f64, d_virial9)
+                       d_types, B, n_table, NN, d_mu, (int)K, (int)n_types, gap, r_cut, d_table, d_energy, d_force, out_f64, d_virial9)
 #define HTF_AF1(VIR, CUT, LM)                                                                                                        \
     do {                                                                                                                             \
         if (nlist_dtype == HTF_F32) HTF_AF(VIR, CUT, LM, float, float4); else HTF_AF(VIR, CUT, LM, double, double4);                 \
@@ -479,6 +486,14 @@ extern "C" int htf_ang_forces(const void *d_nlist, int nlist_dtype, const int *d
 #undef HTF_AF1
 #undef HTF_AF
     return check_launch("ang_force_kernel");
+}
+
+// (the table is the pair tensor's own rows)
+extern "C" int htf_ang_forces(const void *d_nlist, int nlist_dtype, const int *d_index, const float *d_types, unsigned B, unsigned NN,
+                              unsigned K, unsigned n_types, const float *d_mu, float gap, const float *d_table, const float *d_energy,
+                              void *d_force, int force_dtype, void *d_virial9, float r_cut, unsigned l_max, htf_stream stream) {
+    return htf_ang_forces_ghost(d_nlist, nlist_dtype, d_index, d_types, B, NN, K, n_types, d_mu, gap, d_table, d_energy, d_force,
+                                force_dtype, d_virial9, r_cut, l_max, B, stream);
 }
 
 extern "C" int htf_ang_descriptor(const void *d_nlist, int nlist_dtype, unsigned B, unsigned NN, unsigned K, unsigned n_types,

@@ -13,6 +13,7 @@
 // indices and the gathered rows of g alone.  Built with -ffp-contract=on like bp.o (csrc/Makefile), so that pass 1 forms
 // the energy bit for bit as the force kernel does.
 #include "htf_cforce.h"
+#include "htf_cghost.h"
 #include "desc_row.h"
 
 namespace htf {
@@ -27,11 +28,12 @@ __global__ __launch_bounds__(256) void cf_grad_kernel(const typename Vec4<IT>::t
 }
 
 // WIDE: K % 4 == 0 and g is 16-byte aligned (the launcher checks both): a slot's run of g is read as K / 4 float4.
+// n_table >= B: the rows of g (include/htf_cghost.h); rows [B, n_table) are ghosts' rows, read through a slot's index only.
 template <bool VIRIAL, bool CUT, bool WIDE, typename IT>
 __global__ __launch_bounds__(256) void cf_pair_force_kernel(const typename Vec4<IT>::type *__restrict__ nlist,
                                                             const int *__restrict__ index, const float *__restrict__ types, unsigned B,
-                                                            unsigned NN, const float *__restrict__ mu, int K, int T, float gap, float rc,
-                                                            const float *__restrict__ g, const float *__restrict__ energy,
+                                                            unsigned n_table, unsigned NN, const float *__restrict__ mu, int K, int T,
+                                                            float gap, float rc, const float *__restrict__ g, const float *__restrict__ energy,
                                                             void *__restrict__ out, int out_f64, void *__restrict__ virial9) {
     extern __shared__ float s_mem[];
     constexpr int KV = WIDE ? 4 : 1;
@@ -47,6 +49,9 @@ __global__ __launch_bounds__(256) void cf_pair_force_kernel(const typename Vec4<
     const unsigned lane = threadIdx.x & 63u;
     const unsigned ns = (NN + 63u) >> 6;            // slots per lane in use (wave-uniform)
     const unsigned stride = gridDim.x * (blockDim.x >> 6);
+    // the index bound in a vector register: as one more scalar held across the row loop it spilled two SGPRs in three forms
+    unsigned n_index = n_table;
+    asm volatile("" : "+v"(n_index));
 
     for (unsigned row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); row < B; row += stride) { // wave-uniform
         const typename Vec4<IT>::type *rp = nlist + (size_t)row * NN;
@@ -81,7 +86,7 @@ __global__ __launch_bounds__(256) void cf_pair_force_kernel(const typename Vec4<
             }
         }
 
-        // 2. where each slot's reverse term lives: g[j][t_i K ..], or nowhere (index outside [0, B), own type out of range)
+        // 2. where each slot's reverse term lives: g[j][t_i K ..], or nowhere (index outside [0, n_table), own type out of range)
         int ti = 0;
         if (T > 1) {
             const float tw = rintf(types[row]);
@@ -93,7 +98,7 @@ __global__ __launch_bounds__(256) void cf_pair_force_kernel(const typename Vec4<
             gj[t] = nullptr;
             if ((unsigned)t < ns && near[t] && ti >= 0) {   // (a kept slot: t * 64 + lane < NN)
                 const int j = ip[t * 64 + lane];
-                if ((unsigned)j < B) gj[t] = g + ((size_t)j * D + ti * K);
+                if ((unsigned)j < n_index) gj[t] = g + ((size_t)j * D + ti * K);
             }
         }
         line_publish(s_x, lane, (int)lane < D ? g[(size_t)row * D + lane] : 0.f);
@@ -199,10 +204,12 @@ extern "C" int htf_cf_grad(const void *d_nlist, int nlist_dtype, unsigned B, uns
     return check_launch("cf_grad_kernel");
 }
 
-extern "C" int htf_cf_forces(const void *d_nlist, int nlist_dtype, const int *d_index, const float *d_types, unsigned B, unsigned NN,
-                             unsigned K, unsigned n_types, const float *d_mu, float gap, const float *d_g, const float *d_energy,
-                             void *d_force, int force_dtype, void *d_virial9, float r_cut, htf_stream stream) {
+extern "C" int htf_cf_forces_ghost(const void *d_nlist, int nlist_dtype, const int *d_index, const float *d_types, unsigned B,
+                                   unsigned NN, unsigned K, unsigned n_types, const float *d_mu, float gap, const float *d_g,
+                                   const float *d_energy, void *d_force, int force_dtype, void *d_virial9, float r_cut,
+                                   unsigned n_table, htf_stream stream) {
     using namespace htf;
+    HTF_REQUIRE(n_table >= B, "descriptor network: n_table %u < B %u", n_table, B);
     int rc = desc_check(d_nlist, nlist_dtype, B, NN, K, n_types, d_mu, gap, d_force, force_dtype);
     if (rc != HTF_OK) return rc;
     if ((rc = desc_check_rows(B, B, r_cut)) != HTF_OK) return rc;
@@ -215,7 +222,7 @@ extern "C" int htf_cf_forces(const void *d_nlist, int nlist_dtype, const int *d_
     const hipStream_t s = (hipStream_t)stream;
 #define HTF_CF(VIR, CUT, WIDE, T, V4)                                                                                                \
     hipLaunchKernelGGL((cf_pair_force_kernel<VIR, CUT, WIDE, T>), dim3(desc_grid(B)), dim3(256), lds, s, (const V4 *)d_nlist, d_index, \
-                       d_types, B, NN, d_mu, (int)K, (int)n_types, gap, r_cut, d_g, d_energy, d_force, out_f64, d_virial9)
+                       d_types, B, n_table, NN, d_mu, (int)K, (int)n_types, gap, r_cut, d_g, d_energy, d_force, out_f64, d_virial9)
 #define HTF_CF1(VIR, CUT, WIDE)                                                                                                      \
     do {                                                                                                                             \
         if (nlist_dtype == HTF_F32) HTF_CF(VIR, CUT, WIDE, float, float4); else HTF_CF(VIR, CUT, WIDE, double, double4);             \
@@ -233,4 +240,12 @@ extern "C" int htf_cf_forces(const void *d_nlist, int nlist_dtype, const int *d_
 #undef HTF_CF1
 #undef HTF_CF
     return check_launch("cf_pair_force_kernel");
+}
+
+// (the table is the pair tensor's own rows)
+extern "C" int htf_cf_forces(const void *d_nlist, int nlist_dtype, const int *d_index, const float *d_types, unsigned B, unsigned NN,
+                             unsigned K, unsigned n_types, const float *d_mu, float gap, const float *d_g, const float *d_energy,
+                             void *d_force, int force_dtype, void *d_virial9, float r_cut, htf_stream stream) {
+    return htf_cf_forces_ghost(d_nlist, nlist_dtype, d_index, d_types, B, NN, K, n_types, d_mu, gap, d_g, d_energy, d_force,
+                               force_dtype, d_virial9, r_cut, B, stream);
 }

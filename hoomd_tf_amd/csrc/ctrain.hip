@@ -7,6 +7,7 @@
 // one reduction.  Every term lands on the row that reads it: no atomics, no scatter.  Built with -ffp-contract=on like bp.o
 // (csrc/Makefile), so that the shared steps form the same values.
 #include "htf_ctrain.h"
+#include "htf_cghost.h"
 #include "dtrain_row.h"
 
 namespace htf {
@@ -24,11 +25,13 @@ __global__ __launch_bounds__(256, 1) void ct_sweep_kernel(const typename Vec4<IT
 } // namespace
 } // namespace htf
 
-extern "C" int htf_ct_loss_grad(const void *d_nlist, int nlist_dtype, const int *d_index, unsigned B, unsigned NN, unsigned K,
-                                unsigned n_types, unsigned H1, unsigned H2, int activation, const float *d_weights, const float *d_mu,
-                                float gap, const float *d_rho, float *d_accum, float *d_scratch, const int *d_rows, unsigned n_rows,
-                                float r_cut, htf_stream stream) {
+// (the sweep has kept the row count n and the index bound apart from the start: the bound is the residual table's n_table rows)
+extern "C" int htf_ct_loss_grad_ghost(const void *d_nlist, int nlist_dtype, const int *d_index, unsigned B, unsigned NN, unsigned K,
+                                      unsigned n_types, unsigned H1, unsigned H2, int activation, const float *d_weights,
+                                      const float *d_mu, float gap, const float *d_rho, float *d_accum, float *d_scratch,
+                                      const int *d_rows, unsigned n_rows, float r_cut, unsigned n_table, htf_stream stream) {
     using namespace htf;
+    HTF_REQUIRE(n_table >= B, "descriptor network: n_table %u < B %u", n_table, B);
     // (the residual table stands where htf_bp_loss_grad has the labels and the prediction)
     int rc = dtrain_check_call(d_nlist, nlist_dtype, B, NN, K, n_types, H1, H2, activation, d_weights, d_mu, gap, d_rho, HTF_F32, d_rho,
                                d_accum, d_scratch);
@@ -43,7 +46,7 @@ extern "C" int htf_ct_loss_grad(const void *d_nlist, int nlist_dtype, const int 
         const size_t lds = dtrain_lds(K, n_types, H1, H2);
 #define HTF_CT(TANH, CUT, LIST, T, V4)                                                                                                 \
     hipLaunchKernelGGL((ct_sweep_kernel<TANH, CUT, LIST, T>), dim3(grid), dim3(256), lds, s, (const V4 *)d_nlist, d_index, d_rows,      \
-                       n_rows, B, NN, d_weights, d_mu, (int)K, (int)n_types, (int)H1, (int)H2, gap, r_cut, (const float4 *)d_rho,       \
+                       n_rows, n_table, NN, d_weights, d_mu, (int)K, (int)n_types, (int)H1, (int)H2, gap, r_cut, (const float4 *)d_rho, \
                        d_scratch)
 #define HTF_CT1(TANH, CUT, LIST)                                                                                                       \
     do {                                                                                                                               \
@@ -65,4 +68,12 @@ extern "C" int htf_ct_loss_grad(const void *d_nlist, int nlist_dtype, const int 
         if (rl != HTF_OK) return rl;
     }
     return dtrain_reduce_launch(d_scratch, grid, n, d_accum, s);
+}
+
+extern "C" int htf_ct_loss_grad(const void *d_nlist, int nlist_dtype, const int *d_index, unsigned B, unsigned NN, unsigned K,
+                                unsigned n_types, unsigned H1, unsigned H2, int activation, const float *d_weights, const float *d_mu,
+                                float gap, const float *d_rho, float *d_accum, float *d_scratch, const int *d_rows, unsigned n_rows,
+                                float r_cut, htf_stream stream) {
+    return htf_ct_loss_grad_ghost(d_nlist, nlist_dtype, d_index, B, NN, K, n_types, H1, H2, activation, d_weights, d_mu, gap, d_rho,
+                                  d_accum, d_scratch, d_rows, n_rows, r_cut, B, stream);
 }

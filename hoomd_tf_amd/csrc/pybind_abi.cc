@@ -22,6 +22,7 @@
 #include "htf_angular.h"
 #include "htf_ctrain.h"
 #include "htf_atrain.h"
+#include "htf_cghost.h"
 
 namespace py = pybind11;
 
@@ -209,6 +210,13 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
 #define HTF_AT_FUNCTIONS(X) \
     X(htf_at_loss_grad)
 
+// include/htf_cghost.h: the conservative forces and their sweeps on one domain's rows (_lib.CGHOST_PROTOTYPES)
+#define HTF_CGHOST_FUNCTIONS(X) \
+    X(htf_cf_forces_ghost) \
+    X(htf_ang_forces_ghost) \
+    X(htf_ct_loss_grad_ghost) \
+    X(htf_at_loss_grad_ghost)
+
 PYBIND11_MODULE(_htf_abi, m) {
     m.doc() = "pybind11 binding of libhtf_amd.so's C ABI: pointers as integers";
     // a stale module (or library): this module's templates were instantiated from one header, the library it resolved at load
@@ -228,5 +236,6 @@ PYBIND11_MODULE(_htf_abi, m) {
     HTF_CT_FUNCTIONS(X)
     HTF_ANG_FUNCTIONS(X)
     HTF_AT_FUNCTIONS(X)
+    HTF_CGHOST_FUNCTIONS(X)
 #undef X
 }

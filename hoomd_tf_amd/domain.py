@@ -456,3 +456,30 @@ class SlabDomain:
         """Per-step forward halo, blocking form."""
         self.exchange_begin()
         self.exchange_end()
+
+    def halo_rows(self, table, n_local):
+        """Blocking forward halo of per-particle rows on the plan of ``exchange_begin``: ``table`` is a contiguous fp32 tensor
+        [n_local + n_ghost, ...] whose rows ``[0, n_local)`` this rank has written; rows ``table[send_left]`` and
+        ``table[send_right]`` go to the neighbors, and theirs arrive in ``table[n_local : n_local + n_from_left]`` and
+        ``table[n_local + n_from_left : n_local + n_ghost]``, so that ghost row ``n_local + q`` holds what its owner computed for
+        the particle whose position is ``pos[N + q]``.  What a conservative DescriptorMLP gathers per slot (g, the {g, p, S}
+        table, the residual) travels this way between its two sweeps (include/htf_cghost.h).  Always through ``_post``
+        (torch.distributed; gloo stages through the host as for positions), in order with the current stream.  It uses the
+        position halo's tags, so it raises while one is pending.  ``world == 1``: nothing to do."""
+        if self.world == 1:
+            return table
+        if self.pending:
+            raise RuntimeError("SlabDomain.halo_rows: a position exchange is pending (exchange_begin without exchange_end); "
+                               "both use the same message tags")
+        if self.send_left is None:
+            raise RuntimeError("SlabDomain.halo_rows: no send plan yet; call rebuild() first")
+        n_local, n_ghost = int(n_local), self.n_from_left + self.n_from_right
+        if (not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or not table.is_contiguous()
+                or table.dim() < 1 or table.shape[0] != n_local + n_ghost):
+            raise ValueError("SlabDomain.halo_rows: table must be a contiguous fp32 tensor of %d + %d rows, got %s" % (
+                n_local, n_ghost, (tuple(table.shape), table.dtype) if isinstance(table, torch.Tensor) else type(table)))
+        if n_local != self.sys.N:
+            raise ValueError("SlabDomain.halo_rows: n_local = %d, the slab holds %d particles" % (n_local, self.sys.N))
+        self._swap_into(table[self.send_left[0]:self.send_left[1]], table[self.send_right[0]:self.send_right[1]],
+                        table[n_local + self.n_from_left:n_local + n_ghost], table[n_local:n_local + self.n_from_left])
+        return table

@@ -333,7 +333,10 @@ class DescriptorMLP:
     tensor (both calls produce the same slots).  With ``n_types > 1`` it also needs the rows' own types:
     ``layer(nlist, positions)``.  The forces are exact when the list is symmetric within the descriptor's range -- full
     lists, no overflow, ``r_cut`` not above the list's cutoff -- which is not checked.  Energies are the row operator's, bit
-    for bit.  Not with batches, domain decomposition or a mapped list: each raises.
+    for bit.  Under slab domain decomposition (``domain.SlabDomain``) the second sweep also gathers from ghost particles, whose
+    rows of ``g`` their owners compute: one more forward halo between the two sweeps (``SlabDomain.halo_rows``, ``total_forces``'
+    ``n_ghost`` and ``halo``) makes every rank's forces the single-domain forces, and the force-matching sweeps below exchange
+    the residual the same way and all-reduce ``accum``.  Not with batches, a mapped list or a ``BrickDomain``: each raises.
 
     ``trainable="total"`` is force matching on those forces (htf_ct_loss_grad, include/htf_ctrain.h) and implies
     ``conservative=True``: the layer is fitted to the force definition it runs with.  Under ``tfcompute.attach(...,
@@ -558,14 +561,36 @@ class DescriptorMLP:
             index = torch.round(index.detach()).to(torch.int32) if index.is_floating_point() else index.to(torch.int32)
         return index.contiguous()
 
-    def total_forces(self, x, index, virial=False, types=None, species=None):
+    @staticmethod
+    def _ghost_rows(n_ghost, halo, what):
+        """``n_ghost`` as an int; ghost rows without a ``halo`` to fill them raise."""
+        if isinstance(n_ghost, bool) or int(n_ghost) != n_ghost or int(n_ghost) < 0:
+            raise ValueError("DescriptorMLP: %s(n_ghost=%r): a row count, 0 or more" % (what, n_ghost))
+        n_ghost = int(n_ghost)
+        if n_ghost and halo is None:
+            raise ValueError("DescriptorMLP: %s(n_ghost=%d) needs halo=: the callable that fills the ghosts' rows of the table "
+                             "(SlabDomain.halo_rows under domain decomposition)" % (what, n_ghost))
+        if n_ghost and not callable(halo):
+            raise ValueError("DescriptorMLP: %s(halo=%r) is not callable" % (what, halo))
+        return n_ghost
+
+    def total_forces(self, x, index, virial=False, types=None, species=None, n_ghost=0, halo=None):
         """The forces of the total energy, ``F = -d(sum_i E_i)/dr`` (include/htf_cforce.h), on a pair-vector tensor ``x``
         [B, NN, 4] (fp32 or fp64): [B, 4] in ``x``'s dtype with ``E_i`` (``forces``' bits) in column 3, and with ``virial``
         the [B, 3, 3] ``W_i = -1/2 sum_s x_ij (outer) phi_is``.  ``index`` [B, NN]: the particle in each slot, int32 or a float
         tensor taken by ``rint``; a value outside ``[0, B)`` leaves that slot without its reverse term.  ``types``: the rows'
         own types, [B] or [B, 4] (column 3), required when ``n_types > 1``.  ``species`` as for ``forces``.  Equal to the
         gradient when the list is symmetric within the descriptor's range (full lists, no overflow, ``r_cut`` not above the
-        list's cutoff); not checked."""
+        list's cutoff); not checked.
+
+        ``n_ghost > 0``: ``x`` holds the rows of one domain and ``index`` also names ``n_ghost`` ghost particles, numbered
+        ``B .. B + n_ghost - 1`` (include/htf_cghost.h).  The table the second sweep gathers from -- ``g``, or ``{g, p, S}`` with
+        ``l_max > 0`` -- then has ``B + n_ghost`` rows: the first sweep writes rows ``[0, B)``, ``halo(table)`` is called once and
+        must fill rows ``[B, B + n_ghost)`` in place with what the ghosts' owners computed, with work ordered on the current
+        stream (``SlabDomain.halo_rows``), and the second sweep reads a reverse term for every index in ``[0, B + n_ghost)``.
+        The rows then carry the bits the whole system's call gives them.  Without ``halo`` it raises; with ``n_ghost = 0`` the
+        ``halo`` is not called."""
+        n_ghost = self._ghost_rows(n_ghost, halo, "total_forces")
         B, NN = self._check(x)
         index = self._slot_index(index, x)
         own = None
@@ -585,21 +610,35 @@ class DescriptorMLP:
         act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
         launches, rows = self._launches(species, x)
         if self.l_max:   # include/htf_angular.h: the table {g, p, S} per row and channel in place of g
-            h = torch.empty((B, self.Dr, 4 if self.l_max == 1 else 10), dtype=torch.float32, device=x.device)
+            h = torch.empty((B + n_ghost, self.Dr, 4 if self.l_max == 1 else 10), dtype=torch.float32, device=x.device)
             for _, d_rows, n_rows, d_w in launches:
                 check(lib.htf_ang_grad(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, d_w,
                                        self.mu.data_ptr(), float(self.gap), h.data_ptr(), e.data_ptr(), d_rows, n_rows,
                                        float(self.r_cut or 0.0), self.l_max, ops._stream(x)))
+            if n_ghost:
+                halo(h)
+                check(lib.htf_ang_forces_ghost(x.data_ptr(), ops._dt(x), index.data_ptr(), own.data_ptr() if own is not None else None,
+                                               B, NN, self.K, self.n_types, self.mu.data_ptr(), float(self.gap), h.data_ptr(),
+                                               e.data_ptr(), out.data_ptr(), ops._dt(out), v.data_ptr() if v is not None else None,
+                                               float(self.r_cut or 0.0), self.l_max, B + n_ghost, ops._stream(x)))
+                return (out, v) if virial else out
             check(lib.htf_ang_forces(x.data_ptr(), ops._dt(x), index.data_ptr(), own.data_ptr() if own is not None else None, B,
                                      NN, self.K, self.n_types, self.mu.data_ptr(), float(self.gap), h.data_ptr(), e.data_ptr(),
                                      out.data_ptr(), ops._dt(out), v.data_ptr() if v is not None else None,
                                      float(self.r_cut or 0.0), self.l_max, ops._stream(x)))
             return (out, v) if virial else out
-        g = torch.empty((B, self.D), dtype=torch.float32, device=x.device)
+        g = torch.empty((B + n_ghost, self.D), dtype=torch.float32, device=x.device)
         for _, d_rows, n_rows, d_w in launches:   # pass 1: every row is in exactly one list
             check(lib.htf_cf_grad(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, d_w,
                                   self.mu.data_ptr(), float(self.gap), g.data_ptr(), e.data_ptr(), d_rows, n_rows,
                                   float(self.r_cut or 0.0), ops._stream(x)))
+        if n_ghost:
+            halo(g)
+            check(lib.htf_cf_forces_ghost(x.data_ptr(), ops._dt(x), index.data_ptr(), own.data_ptr() if own is not None else None, B,
+                                          NN, self.K, self.n_types, self.mu.data_ptr(), float(self.gap), g.data_ptr(), e.data_ptr(),
+                                          out.data_ptr(), ops._dt(out), v.data_ptr() if v is not None else None,
+                                          float(self.r_cut or 0.0), B + n_ghost, ops._stream(x)))
+            return (out, v) if virial else out
         check(lib.htf_cf_forces(x.data_ptr(), ops._dt(x), index.data_ptr(), own.data_ptr() if own is not None else None, B, NN,
                                 self.K, self.n_types, self.mu.data_ptr(), float(self.gap), g.data_ptr(), e.data_ptr(),
                                 out.data_ptr(), ops._dt(out), v.data_ptr() if v is not None else None,
@@ -662,7 +701,7 @@ class DescriptorMLP:
                 accum.view(S, 1 + P)[s].zero_()
         return pred, accum, launches, rows, scratch
 
-    def total_loss_gradient(self, x, labels, index, types=None, pred=None, accum=None, species=None):
+    def total_loss_gradient(self, x, labels, index, types=None, pred=None, accum=None, species=None, n_ghost=0, halo=None):
         """One force-matching sweep on the forces of the total energy (htf_ct_loss_grad, include/htf_ctrain.h): ``accum`` as
         ``loss_gradient`` returns it -- [1 + P], or [S, 1 + P] with zero rows for absent species -- for the residuals of
         ``total_forces(x, index, ...)`` against ``labels`` [B, 4], so that the fit and a ``conservative=True`` run see the same
@@ -670,34 +709,58 @@ class DescriptorMLP:
         ``pred`` [B, 4] fp32: ``total_forces`` at the current weights, evaluated here (with ``types``, which the sweep itself
         does not need) when not given.  The residual ``pred - labels`` is formed in fp32 with torch and every row's is read:
         ``x`` holds the whole system.  Two calls on the same inputs give the same bits.  Callable on any layer, like
-        ``total_forces``."""
+        ``total_forces``.
+
+        ``n_ghost > 0`` (as for ``total_forces``): ``x`` holds one domain's rows; the residual table has ``B + n_ghost`` rows,
+        ``halo(rho)`` fills the ghosts' rows with their owners' residuals, and ``pred``, when not given, is ``total_forces``
+        with the same ``n_ghost`` and ``halo``.  ``accum`` then holds this domain's rows' share: the sum over the domains is the
+        whole system's sweep."""
         if self.l_max:
             raise NotImplementedError("DescriptorMLP: total_loss_gradient() is the sweep of an l_max = 0 layer; with l_max = %d its "
                                       "follow-up angular_loss_gradient(x, labels, index) is the force-matching sweep" % self.l_max)
-        return self._conservative_sweep(x, labels, index, types, pred, accum, species)
+        return self._conservative_sweep(x, labels, index, types, pred, accum, species, n_ghost, halo, "total_loss_gradient")
 
-    def angular_loss_gradient(self, x, labels, index, types=None, pred=None, accum=None, species=None):
+    def angular_loss_gradient(self, x, labels, index, types=None, pred=None, accum=None, species=None, n_ghost=0, halo=None):
         """``total_loss_gradient`` for a layer with ``l_max = 1`` or ``2`` (htf_at_loss_grad, include/htf_atrain.h): one
         force-matching sweep on the forces of the total energy with angular channels.  Argument for argument the same: ``accum``
         [1 + P], or [S, 1 + P] with zero rows for absent species, holds {SSR, d SSR / d theta} per network for the residuals of
         ``total_forces(x, index, ...)`` against ``labels`` [B, 4]; ``pred`` [B, 4] fp32 is ``total_forces`` at the current
         weights, evaluated here when not given; the residual is formed in fp32 with torch; a slot whose index is outside
         ``[0, B)`` has no reverse term.  Two calls on the same inputs give the same bits.  Callable on any layer with
-        ``l_max > 0``, trainable or not; with ``l_max = 0`` it raises."""
+        ``l_max > 0``, trainable or not; with ``l_max = 0`` it raises.  ``n_ghost`` and ``halo`` as for ``total_loss_gradient``."""
         if not self.l_max:
             raise ValueError("DescriptorMLP: angular_loss_gradient() is the sweep of the angular channels (l_max = 1 or 2); "
                              "total_loss_gradient(x, labels, index) is the sweep of this l_max = 0 layer")
-        return self._conservative_sweep(x, labels, index, types, pred, accum, species)
+        return self._conservative_sweep(x, labels, index, types, pred, accum, species, n_ghost, halo, "angular_loss_gradient")
 
-    def _conservative_sweep(self, x, labels, index, types, pred, accum, species):
-        """The sweep on the forces of the total energy for this layer's ``l_max``: htf_ct_loss_grad, or htf_at_loss_grad."""
+    def _conservative_sweep(self, x, labels, index, types, pred, accum, species, n_ghost=0, halo=None, what="total_loss_gradient"):
+        """The sweep on the forces of the total energy for this layer's ``l_max``: htf_ct_loss_grad, or htf_at_loss_grad; with
+        ghost rows their twins of include/htf_cghost.h on the residual table of ``B + n_ghost`` rows."""
+        n_ghost = self._ghost_rows(n_ghost, halo, what)
         B, NN = self._check(x)
         index = self._slot_index(index, x)
         pred, accum, launches, rows, scratch = self._sweep_buffers(
-            x, labels, pred, accum, species, lambda: self.total_forces(x, index, types=types, species=species))
-        rho = (pred.detach() - labels.detach().to(torch.float32)).contiguous()
+            x, labels, pred, accum, species,
+            lambda: self.total_forces(x, index, types=types, species=species, n_ghost=n_ghost, halo=halo))
         P = self.P
         act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
+        if n_ghost:
+            rho = torch.empty((B + n_ghost, 4), dtype=torch.float32, device=x.device)
+            torch.sub(pred.detach(), labels.detach().to(torch.float32), out=rho[:B])
+            halo(rho)
+            for s, d_rows, n_rows, d_w in launches:
+                if self.l_max:
+                    check(lib.htf_at_loss_grad_ghost(x.data_ptr(), ops._dt(x), index.data_ptr(), B, NN, self.K, self.n_types, self.H1,
+                                                     self.H2, act, d_w, self.mu.data_ptr(), float(self.gap), rho.data_ptr(),
+                                                     accum.data_ptr() + 4 * s * (1 + P), scratch.data_ptr(), d_rows, n_rows,
+                                                     float(self.r_cut or 0.0), self.l_max, B + n_ghost, ops._stream(x)))
+                else:
+                    check(lib.htf_ct_loss_grad_ghost(x.data_ptr(), ops._dt(x), index.data_ptr(), B, NN, self.K, self.n_types, self.H1,
+                                                     self.H2, act, d_w, self.mu.data_ptr(), float(self.gap), rho.data_ptr(),
+                                                     accum.data_ptr() + 4 * s * (1 + P), scratch.data_ptr(), d_rows, n_rows,
+                                                     float(self.r_cut or 0.0), B + n_ghost, ops._stream(x)))
+            return accum
+        rho = (pred.detach() - labels.detach().to(torch.float32)).contiguous()
         for s, d_rows, n_rows, d_w in launches:
             if self.l_max:
                 check(lib.htf_at_loss_grad(x.data_ptr(), ops._dt(x), index.data_ptr(), B, NN, self.K, self.n_types, self.H1, self.H2,

@@ -67,11 +67,14 @@ class Nlist(_TorchOperand):
     needs.  ``nlist[:, :, :3]`` stays symbolic for the declarative layers; torch code gets
     the autograd leaf ``ad``.  ``index``: the int32 ``[N, NN]`` tensor of the particle in each slot (-1: empty), or a
     callable that builds it; it is built when ``.index`` is first read (a conservative DescriptorMLP reads it), None when the
-    list came without one."""
+    list came without one.  ``ghost``: ``(n_ghost, halo)`` -- how many ghost particles, numbered from N up, the index names beyond
+    the N rows, and the callable that fills their rows of a per-particle table (``DescriptorMLP.total_forces``) -- or a callable
+    that returns the pair, read as lazily; None: no ghost rows."""
 
-    def __init__(self, tensor, index=None):
+    def __init__(self, tensor, index=None, ghost=None):
         self.tensor = tensor
         self._index = index
+        self._ghost = ghost
         self._ad = None
         self._weights = []      # the scalar weights traced expressions of this list read: [(leaf tensor, flat index), ...] -> p.theta[k]
 
@@ -90,6 +93,12 @@ class Nlist(_TorchOperand):
         if callable(self._index):
             self._index = self._index()
         return self._index
+
+    @property
+    def ghost(self):
+        if callable(self._ghost):
+            self._ghost = self._ghost()
+        return self._ghost
 
     def weight_index(self, leaf, flat):
         """k of (leaf, flat) in this trace's weight vector (appended on first sight)."""
@@ -1728,7 +1737,9 @@ def compute_nlist_forces(nlist, energy, virial=False):
                 raise ValueError("a conservative DescriptorMLP with n_types = %d needs the particles' own types: "
                                  "layer(nlist, positions)" % lay.n_types)
             types = _unwrap(energy.positions)[:nl.tensor.shape[0]] if lay.n_types > 1 else None
-            out = lay.total_forces(nl.tensor, index, virial, types=types, species=energy.species)
+            # (a slab's list also names ghost particles: their rows of the gathered table come from their owners)
+            n_ghost, halo = (nl if nl.index is not None else energy.nlist).ghost or (0, None)
+            out = lay.total_forces(nl.tensor, index, virial, types=types, species=energy.species, n_ghost=n_ghost, halo=halo)
         else:
             out = lay.forces(nl.tensor, virial, species=energy.species)
         entry = {"op": "descriptor_mlp", "species": energy.species}   # (no plan: a model calling it keeps the eager path)
@@ -1736,6 +1747,8 @@ def compute_nlist_forces(nlist, energy, virial=False):
             # what tfcompute's training step needs (no "potential": the layer's own sweep trains it, DescriptorMLP.loss_gradient,
             # or total_loss_gradient on the slot index and the types a conservative layer has just used)
             entry.update(layer=energy.layer, nlist=nl, forces=out[0] if virial else out, index=index, types=types)
+            if getattr(lay, "conservative", False):
+                entry.update(n_ghost=n_ghost, halo=halo)
         _trace_log().append(entry)
         return out
     if isinstance(energy, BiasedEnergy):

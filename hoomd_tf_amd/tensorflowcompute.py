@@ -413,9 +413,21 @@ class tfcompute:
         the batch's pair vectors (DescriptorMLP.loss_gradient, or total_loss_gradient for trainable="total", with the forces the
         model has just evaluated as the prediction), optimizer step on the layer's flat weights on the device."""
         domain = getattr(self._nlist, "domain", None)
-        if domain is not None and domain.world > 1:
-            raise NotImplementedError("training a DescriptorMLP over several ranks is not implemented")
         m, layer = self.model, entry["layer"]
+        ranks = domain is not None and domain.world > 1
+        if ranks:
+            # data-parallel over the slabs, as _train_on_batch: every rank sweeps its own rows (a conservative layer with the
+            # ghosts' residuals from their owners), ONE all-reduce of [SSR, gradient] per step keeps the replicas' weights identical
+            if getattr(domain, "fixed_capacity", False) or domain.local_counts is None:
+                raise NotImplementedError("training a DescriptorMLP over the ranks of a BrickDomain is not implemented: a "
+                                          "SlabDomain trains it")
+            if self.batch_size:
+                raise NotImplementedError("training a DescriptorMLP over several ranks in batches (batch_size = %d) is not "
+                                          "implemented: the ranks would disagree on the number of all-reduces; batch_size = 0 "
+                                          "takes a rank's rows in one" % self.batch_size)
+            if getattr(layer, "n_species", 1) > 1:
+                raise NotImplementedError("training a DescriptorMLP with n_species = %d over several ranks is not implemented: a "
+                                          "species absent from one rank is stepped on the others" % layer.n_species)
         theta = layer.w
         if getattr(self, "_opt_desc", None) is None:
             self._opt_desc = m.optimizer.desc(layer.nonneg_mask, layer.l1_reg)
@@ -430,17 +442,25 @@ class tfcompute:
             if m.metrics:
                 m.metrics[0].state = self._opt_state
         accum = self._descriptor_sweep(layer, nlist_t, self._labels[offset:offset + n], pred, entry)
-        ops.optimizer_step(theta, accum, 1.0 / (4.0 * float(n)), self._opt_state, self._opt_desc)
+        n_total = float(n)
+        if ranks:
+            import torch.distributed as dist
+            dist.all_reduce(accum, group=domain.group)
+            n_total = float(sum(domain.local_counts))   # (from the last rebuild's counts: no message, no read-back)
+        ops.optimizer_step(theta, accum, 1.0 / (4.0 * n_total), self._opt_state, self._opt_desc)
 
     @staticmethod
     def _descriptor_sweep(layer, nlist_t, labels, pred, entry, species=None):
         """The layer's sweep for the force definition it trains on: the row operator's (trainable=True), or the forces of the
         total energy (trainable="total"; with angular channels, trainable="angular") on the slot index and the types the step's
         own total_forces call used."""
+        ghost = dict(n_ghost=entry.get("n_ghost", 0), halo=entry.get("halo"))   # (a slab's ghost rows: the residual travels too)
         if layer.trainable == "total":
-            return layer.total_loss_gradient(nlist_t, labels, entry["index"], types=entry.get("types"), pred=pred, species=species)
+            return layer.total_loss_gradient(nlist_t, labels, entry["index"], types=entry.get("types"), pred=pred, species=species,
+                                             **ghost)
         if layer.trainable == "angular":
-            return layer.angular_loss_gradient(nlist_t, labels, entry["index"], types=entry.get("types"), pred=pred, species=species)
+            return layer.angular_loss_gradient(nlist_t, labels, entry["index"], types=entry.get("types"), pred=pred, species=species,
+                                               **ghost)
         return layer.loss_gradient(nlist_t, labels, pred=pred, species=species)
 
     def _train_descriptor_species(self, nlist_t, offset, n, layer, pred, entry):
@@ -593,20 +613,40 @@ class tfcompute:
     def _index_provider(self, offset, n):
         """What ``Nlist.index`` of the step's neighbor tensor calls when it is first read: the particle in each slot
         (ops.build_pair_index on the arguments of the step's build_pair_vectors).  A conservative DescriptorMLP reads it, and
-        needs g_j of every neighbor in the same call: it raises where some are elsewhere."""
+        needs g_j of every neighbor in the same call: the rank's own rows, and under a SlabDomain the ghosts' rows through the
+        halo of ``_ghost_rows``; it raises where some are elsewhere."""
         def build():
             s, nl = self.system, self._nlist
             if n < s.N:
                 raise ValueError("a conservative DescriptorMLP needs the whole system in one batch (batch_size %d < N = %d): "
                                  "its forces read dE_j/dG_j of every neighbor j" % (n, s.N))
-            if getattr(nl, "domain", None) is not None or getattr(s, "n_ghost", 0):
-                raise ValueError("a conservative DescriptorMLP does not run under domain decomposition: dE_j/dG_j of ghost "
-                                 "particles is not exchanged")
+            self._ghost_rows()   # (raises for the decompositions whose ghosts' rows are not exchanged)
             if self.model._map_nlist:
                 raise ValueError("a conservative DescriptorMLP does not run on a mapped neighbor list")
             return ops.build_pair_index(s.pos, nl.n_neigh, nl.head_list, nl.nlist, s.box, self.r_cut, self.nneighbor_cutoff,
                                         offset=offset, batch_size=n, n_local=s.N)
         return build
+
+    def _ghost_rows(self):
+        """(n_ghost, halo) of the step's neighbor list for a conservative DescriptorMLP: the ghost rows its index names beyond the
+        rank's own, and the callable that fills them in a table (SlabDomain.halo_rows).  (0, None) on one domain."""
+        from .domain import SlabDomain
+        s, domain = self.system, getattr(self._nlist, "domain", None)
+        if domain is None:
+            if getattr(s, "n_ghost", 0):
+                raise ValueError("a conservative DescriptorMLP met %d ghost rows without a domain on the neighbor list: nobody "
+                                 "exchanges dE_j/dG_j of the ghost particles" % s.n_ghost)
+            return 0, None
+        if not isinstance(domain, SlabDomain):
+            raise ValueError("a conservative DescriptorMLP does not run under a %s: dE_j/dG_j of its ghost particles is not "
+                             "exchanged (a SlabDomain exchanges it)" % type(domain).__name__)
+        if domain.world == 1:
+            return 0, None
+        if not s.n_ghost:
+            raise ValueError("a conservative DescriptorMLP on a slab without ghost rows: its neighbors would wait for this rank's "
+                             "rows of dE_j/dG_j")
+        n_local = s.N
+        return int(s.n_ghost), lambda table: domain.halo_rows(table, n_local)
 
     def _finish_update(self, batch_index, offset, n):
         """tensorflowcompute.py:313-345 (inference branch)."""
@@ -625,6 +665,7 @@ class tfcompute:
         inputs = m.compute_inputs(nlist_t, pos_t, box_t)
         if NN > 0:
             inputs[0]._index = self._index_provider(offset, n)   # (built only when read: a conservative DescriptorMLP)
+            inputs[0]._ghost = self._ghost_rows                  # (likewise: the ghost rows that index names, and their halo)
         mark = len(simmodel._trace_log())
         simmodel._trace.training_graph = bool(self.train)  # generic route: forces stay differentiable
         try:

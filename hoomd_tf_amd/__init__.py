@@ -11,7 +11,9 @@ network ``DescriptorMLP``, its force-matching sweep, smooth cutoff and one netwo
 matching on those forces, ``DescriptorMLP(trainable="total")`` and ``total_loss_gradient``: include/htf_ctrain.h; angular channels on the conservative
 forces, ``DescriptorMLP(conservative=True, l_max=1 or 2)``: include/htf_angular.h; force matching on those, ``DescriptorMLP(l_max=1 or 2,
 trainable="angular")`` and ``angular_loss_gradient``: include/htf_atrain.h; the same forces and sweeps on one slab domain's
-rows, with the ghost particles' table rows from their owners: include/htf_cghost.h).
+rows, with the ghost particles' table rows from their owners: include/htf_cghost.h; a committee of M such networks,
+``DescriptorMLP(conservative=True, n_models=M)``, whose ``total_forces`` gives the mean-model forces and leaves the per-particle
+model deviation in ``layer.deviation``, the descriptor and every exponential formed once for all members: include/htf_committee.h).
 The offline path ``iter_from_trajectory`` / ``ArrayTrajectory`` runs a
 ``SimModel`` over stored frames.
 """

@@ -312,9 +312,18 @@ CGHOST_PROTOTYPES = {
     "htf_at_loss_grad_ghost": (_i, AT_PROTOTYPES["htf_at_loss_grad"][1][:-1] + [_u, _vp]),
 }
 
+# a committee of descriptor networks (include/htf_committee.h; DescriptorMLP(n_models=M)): htf_cf_grad's arguments with
+# ``unsigned n_models, unsigned weight_stride`` before the stream, htf_cf_forces' with ``unsigned n_models, float *d_dev,
+# float *d_members``
+CMT_PROTOTYPES = {
+    "htf_cmt_grad": (_i, CF_PROTOTYPES["htf_cf_grad"][1][:-1] + [_u, _u, _vp]),
+    "htf_cmt_forces": (_i, CF_PROTOTYPES["htf_cf_forces"][1][:-1] + [_u, _vp, _vp, _vp]),
+}
+
 # every table above: what the ctypes and the pybind11 binding both declare
 ALL_PROTOTYPES = tuple((name, proto) for table in (PROTOTYPES, STANDIN_PROTOTYPES, STEP_CHECK_PROTOTYPES, CG_PROTOTYPES, GEOM_PROTOTYPES, NLIST_PROTOTYPES,
-                                                   BP_PROTOTYPES, CF_PROTOTYPES, CT_PROTOTYPES, ANG_PROTOTYPES, AT_PROTOTYPES, CGHOST_PROTOTYPES)
+                                                   BP_PROTOTYPES, CF_PROTOTYPES, CT_PROTOTYPES, ANG_PROTOTYPES, AT_PROTOTYPES, CGHOST_PROTOTYPES,
+                                                   CMT_PROTOTYPES)
                        for name, proto in table.items())
 
 

@@ -19,6 +19,7 @@
 #include "htf_nlist.h"
 #include "htf_bp.h"
 #include "htf_cforce.h"
+#include "htf_committee.h"
 #include "htf_angular.h"
 #include "htf_ctrain.h"
 #include "htf_atrain.h"
@@ -217,6 +218,11 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
     X(htf_ct_loss_grad_ghost) \
     X(htf_at_loss_grad_ghost)
 
+// include/htf_committee.h: a committee of descriptor networks (_lib.CMT_PROTOTYPES)
+#define HTF_CMT_FUNCTIONS(X) \
+    X(htf_cmt_grad) \
+    X(htf_cmt_forces)
+
 PYBIND11_MODULE(_htf_abi, m) {
     m.doc() = "pybind11 binding of libhtf_amd.so's C ABI: pointers as integers";
     // a stale module (or library): this module's templates were instantiated from one header, the library it resolved at load
@@ -237,5 +243,6 @@ PYBIND11_MODULE(_htf_abi, m) {
     HTF_ANG_FUNCTIONS(X)
     HTF_AT_FUNCTIONS(X)
     HTF_CGHOST_FUNCTIONS(X)
+    HTF_CMT_FUNCTIONS(X)
 #undef X
 }

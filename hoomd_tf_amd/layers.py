@@ -361,20 +361,63 @@ class DescriptorMLP:
     ``iter_from_trajectory``.  The sweep is ``total_loss_gradient``'s over the wider input, its tangent ``[Gdot | Adot | Qdot]``
     formed from the moments and their tangents; it is callable on any layer with ``l_max > 0``.  With ``l_max=0`` the value
     raises and names ``trainable="total"``.
+
+    ``n_models=M`` (2 to 8, with ``conservative=True``; include/htf_committee.h) makes the layer a committee: M members of this
+    one architecture, member ``m`` and species ``s`` initialised from ``mlp_params(seed + m S + s, ...)``, ``w`` holding
+    ``[M][S][P]`` floats and ``get_weights`` / ``set_weights`` / ``save_weights`` / ``load_weights`` carrying a leading axis of
+    length M ahead of the species axis.  ``total_forces`` and ``compute_nlist_forces`` return the mean model, ``Fbar_i = (1/M)
+    sum_m F_i^m`` with ``Ebar_i`` in column 3 and the mean virial when asked, each ``F_i^m`` being the conservative forces above
+    for member ``m``'s weights, and leave in ``layer.deviation`` the [B, 2] fp32 tensor of that call (``None`` before the first),
+    the per-particle model deviation that tells when the model extrapolates::
+
+        devF_i = sqrt((1/M) sum_m |F_i^m - Fbar_i|^2)        devE_i = sqrt((1/M) sum_m (E_i^m - Ebar_i)^2)
+
+    in the population form, computed as written (mean first, then the differences): members that agree have deviation 0.  A
+    model returns it as a second output (``return f, self.desc.deviation``) and finds it in ``tfcompute.outputs``;
+    ``total_forces(..., members=True)`` also returns the [M, B, 4] fp32 tensor of ``(F_i^m, E_i^m)``.  The two sweeps read the
+    slots, form ``G_i`` and evaluate every exponential once for all members; only the dense stack and the gathered ``g_j`` run M
+    times.  The first sweep keeps all M networks in LDS, ``4 (M P4 + K4 + 1024)`` bytes (P4: ``D (H1 + 1) + H1 (H2 + 1) + H1 + 2 H2
+    + 1`` floats, rounded up to a multiple of 4, K4 likewise); a committee above 160 KiB raises at construction.
+    ``layer.member(m)`` is a plain ``DescriptorMLP`` whose ``w`` is a view of member ``m``'s slice: ``forces``,
+    ``total_forces``, ``descriptor``, ``total_loss_gradient`` and ``ops.optimizer_step`` on it evaluate and train that member in
+    place, and the committee sees the new weights at its next call -- this is how a committee is trained, offline.  Not
+    covered, each raises: angular channels (``l_max > 0``), ``trainable`` on the committee itself and
+    ``tfcompute(train=True)``, slab or brick domains (``n_ghost > 0``), and the row-operator and sweep methods, which point to
+    ``member(m)``.  ``n_models=1`` is the layer without the argument.
     Limits: ``n_types * K * (1 + l_max) <= 64``, ``H1, H2 <= 64``, at most 256 neighbor slots."""
 
     name = 'descriptor-mlp'
     _KEYS = ("W1", "b1", "W2", "b2", "W3", "b3")
     MAX_D, MAX_H, MAX_NN = 64, 64, 256
+    MAX_MODELS, MAX_COMMITTEE_LDS = 8, 160 * 1024   # include/htf_committee.h
+    deviation = None    # a committee's (devF_i, devE_i) [B, 2] of its last total_forces call
     nonneg_mask = 0     # what the optimizer step reads of a trainable layer: no weight is constrained or regularised
     l1_reg = (0.0,)
 
     def __init__(self, K=16, H1=32, H2=32, low=0.0, high=3.0, n_types=1, activation="tanh", seed=3, device=None,
-                 trainable=False, r_cut=None, n_species=1, conservative=False, l_max=0):
+                 trainable=False, r_cut=None, n_species=1, conservative=False, l_max=0, n_models=1):
         K, H1, H2, n_types, n_species = int(K), int(H1), int(H2), int(n_types), int(n_species)
         if isinstance(l_max, bool) or int(l_max) != l_max or int(l_max) not in (0, 1, 2):
             raise ValueError("DescriptorMLP: l_max must be 0, 1 or 2, not %r" % (l_max,))
         self.l_max = l_max = int(l_max)
+        if (isinstance(n_models, bool) or not isinstance(n_models, (int, np.integer))
+                or not 1 <= int(n_models) <= self.MAX_MODELS):
+            raise ValueError("DescriptorMLP: n_models must be an integer in [1, %d], not %r: a larger committee is several "
+                             "layers, each evaluated with its own total_forces" % (self.MAX_MODELS, n_models))
+        self.n_models = n_models = int(n_models)
+        if n_models > 1:
+            if l_max:
+                raise NotImplementedError("DescriptorMLP: n_models = %d does not go with l_max = %d: a committee of angular "
+                                          "networks is a follow-up; M layers of l_max = %d, one total_forces each, evaluate it"
+                                          % (n_models, l_max, l_max))
+            if trainable is not False:
+                raise NotImplementedError("DescriptorMLP: n_models = %d does not go with trainable=%r: training a committee in "
+                                          "the running simulation is a follow-up; member(m, trainable=\"total\") is a view of "
+                                          "member m that total_loss_gradient and ops.optimizer_step train in place"
+                                          % (n_models, trainable))
+            if not conservative:
+                raise ValueError("DescriptorMLP: n_models = %d needs conservative=True: the deviation is defined on the forces "
+                                 "of the total energy (total_forces)" % n_models)
         if isinstance(trainable, str):
             if trainable not in ("total", "angular"):
                 raise ValueError("DescriptorMLP: trainable must be False, True, 'total' or 'angular', not %r" % (trainable,))
@@ -422,11 +465,47 @@ class DescriptorMLP:
         self.D = self.Dr * (1 + l_max)
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
-        ps = [mlp_params(seed=seed + s, K=self.D, H1=H1, H2=H2) for s in range(n_species)]
+        if n_models > 1:
+            need = self.committee_lds_bytes(n_models, K, n_types, H1, H2)
+            if need > self.MAX_COMMITTEE_LDS:
+                raise ValueError("DescriptorMLP: a committee of %d networks of %d x %d x %d needs %d bytes of LDS for its first "
+                                 "sweep, above the %d bytes of one compute unit: fewer members, or narrower networks"
+                                 % (n_models, self.D, H1, H2, need, self.MAX_COMMITTEE_LDS))
+        ps = [mlp_params(seed=seed + s, K=self.D, H1=H1, H2=H2) for s in range(n_models * n_species)]   # [M][S]
         self._shapes = [ps[0][k].shape for k in self._KEYS]
         self.P = sum(int(np.prod(sh)) for sh in self._shapes)   # floats of one network
         self.w = torch.tensor(np.concatenate([p[k].ravel() for p in ps for k in self._KEYS]), dtype=torch.float32, device=device)
         self.mu = torch.tensor(self.centers, dtype=torch.float32, device=device)
+
+    @staticmethod
+    def committee_lds_bytes(n_models, K, n_types, H1, H2):
+        """Dynamic LDS of the committee's first sweep (htf_cmt_grad): M networks with rows padded by one float, the centres
+        and one exchange line for each of a block's 16 waves."""
+        D = K * n_types
+        member = (D * (H1 + 1) + H1 + H1 * (H2 + 1) + H2 + H2 + 1 + 3) & ~3
+        return 4 * (n_models * member + ((K + 3) & ~3) + 16 * 64)
+
+    def member(self, m, trainable=False):
+        """Member ``m`` of a committee as a plain ``DescriptorMLP`` of the same configuration (``n_models=1``, ``trainable`` as
+        given) whose ``w`` is a view of this layer's ``w[m S P:(m + 1) S P]``: evaluating it runs the single-network kernels
+        on that member, and training it in place (``total_loss_gradient`` and ``ops.optimizer_step`` on the view) changes what
+        the committee computes at its next call."""
+        if isinstance(m, bool) or int(m) != m or not 0 <= int(m) < self.n_models:
+            raise ValueError("DescriptorMLP: member(%r) of a layer with n_models = %d" % (m, self.n_models))
+        cfg = self.get_config()
+        cfg.pop("n_models", None)
+        cfg.pop("trainable", None)
+        lay = DescriptorMLP(device="cpu", trainable=trainable, **cfg)
+        n = self.n_species * self.P
+        lay.w = self.w[int(m) * n:(int(m) + 1) * n]
+        lay.mu = self.mu
+        return lay
+
+    def _no_committee(self, what):
+        if self.n_models > 1:
+            raise NotImplementedError("DescriptorMLP: %s() is a single network's; on a committee (n_models = %d) member(m).%s() "
+                                      "evaluates member m, and total_forces() the mean model and its deviation"
+                                      % (what, self.n_models, what))
 
     def get_config(self):
         cfg = {'K': self.K, 'H1': self.H1, 'H2': self.H2, 'low': self.low, 'high': self.high, 'n_types': self.n_types,
@@ -441,26 +520,31 @@ class DescriptorMLP:
             cfg['conservative'] = True
         if self.l_max:
             cfg['l_max'] = self.l_max
+        if self.n_models != 1:
+            cfg['n_models'] = self.n_models
         return cfg
 
     def get_weights(self):
-        """The six Keras arrays; with ``n_species = S > 1`` each has a leading axis of length S."""
-        S = self.n_species
-        flat, out, o = self.w.detach().cpu().numpy().reshape(S, self.P), [], 0
+        """The six Keras arrays; with ``n_species = S > 1`` each has a leading axis of length S, and with ``n_models = M > 1``
+        one of length M ahead of it."""
+        lead = self._lead_axes()
+        flat, out, o = self.w.detach().cpu().numpy().reshape(-1, self.P), [], 0
         for shape in self._shapes:
             n = int(np.prod(shape))
-            a = flat[:, o:o + n].reshape((S,) + tuple(shape)).copy()
-            out.append(a if S > 1 else a[0])
+            out.append(flat[:, o:o + n].reshape(lead + tuple(shape)).copy())
             o += n
         return out
 
+    def _lead_axes(self):
+        return ((self.n_models,) if self.n_models > 1 else ()) + ((self.n_species,) if self.n_species > 1 else ())
+
     def set_weights(self, ws):
         ws = list(ws)
-        S = self.n_species
+        S = self.n_models * self.n_species
         if len(ws) != len(self._KEYS):
             raise ValueError("DescriptorMLP: expected %d weight arrays, got %d" % (len(self._KEYS), len(ws)))
         for k, shape, w in zip(self._KEYS, self._shapes, ws):
-            shape = ((S,) if S > 1 else ()) + tuple(shape)
+            shape = self._lead_axes() + tuple(shape)
             if np.shape(w) != shape:
                 raise ValueError("DescriptorMLP: shape mismatch for %s: %r, expected %r" % (k, np.shape(w), shape))
         flat = np.concatenate([np.asarray(w, dtype=np.float32).reshape(S, -1) for w in ws], axis=1).ravel()
@@ -482,7 +566,7 @@ class DescriptorMLP:
         if x.shape[1] > self.MAX_NN:
             raise ValueError("DescriptorMLP: NN = %d neighbor slots; the kernel takes at most %d" % (x.shape[1], self.MAX_NN))
         ops._dev(self.w, "DescriptorMLP.w", torch.float32)
-        if self.w.device != x.device or self.w.numel() != self.n_species * self.P:
+        if self.w.device != x.device or self.w.numel() != self.n_models * self.n_species * self.P:
             raise ValueError("DescriptorMLP: the weights (%d floats on %s) do not fit a call on %s" % (self.w.numel(), self.w.device, x.device))
         return int(x.shape[0]), int(x.shape[1])
 
@@ -533,6 +617,7 @@ class DescriptorMLP:
         [B, 3, 3] virial when ``virial``.  compute_nlist_forces calls this for the layer's energy.  ``species``: [B] or
         [B, 4] (column 3), needed when ``n_species > 1``."""
         self._no_angular("forces")
+        self._no_committee("forces")
         B, NN = self._check(x)
         out = torch.empty((B, 4), dtype=x.dtype, device=x.device)
         v = torch.empty((B, 3, 3), dtype=x.dtype, device=x.device) if virial else None
@@ -574,7 +659,7 @@ class DescriptorMLP:
             raise ValueError("DescriptorMLP: %s(halo=%r) is not callable" % (what, halo))
         return n_ghost
 
-    def total_forces(self, x, index, virial=False, types=None, species=None, n_ghost=0, halo=None):
+    def total_forces(self, x, index, virial=False, types=None, species=None, n_ghost=0, halo=None, members=False):
         """The forces of the total energy, ``F = -d(sum_i E_i)/dr`` (include/htf_cforce.h), on a pair-vector tensor ``x``
         [B, NN, 4] (fp32 or fp64): [B, 4] in ``x``'s dtype with ``E_i`` (``forces``' bits) in column 3, and with ``virial``
         the [B, 3, 3] ``W_i = -1/2 sum_s x_ij (outer) phi_is``.  ``index`` [B, NN]: the particle in each slot, int32 or a float
@@ -589,8 +674,19 @@ class DescriptorMLP:
         must fill rows ``[B, B + n_ghost)`` in place with what the ghosts' owners computed, with work ordered on the current
         stream (``SlabDomain.halo_rows``), and the second sweep reads a reverse term for every index in ``[0, B + n_ghost)``.
         The rows then carry the bits the whole system's call gives them.  Without ``halo`` it raises; with ``n_ghost = 0`` the
-        ``halo`` is not called."""
+        ``halo`` is not called.
+
+        On a committee (``n_models = M > 1``, include/htf_committee.h) the result is the mean model: ``(Fbar_i, Ebar_i)`` and
+        the mean virial, in ``x``'s dtype; ``self.deviation`` becomes this call's [B, 2] fp32 ``(devF_i, devE_i)``, and
+        ``members=True`` appends the [M, B, 4] fp32 tensor of ``(F_i^m, E_i^m)`` to what is returned.  ``n_ghost > 0`` raises
+        there."""
         n_ghost = self._ghost_rows(n_ghost, halo, "total_forces")
+        if self.n_models > 1 and n_ghost:
+            raise NotImplementedError("DescriptorMLP: a committee (n_models = %d) does not run on a domain's rows (n_ghost = %d): "
+                                      "slab domains are a follow-up; member(m).total_forces(..., n_ghost=, halo=) evaluates "
+                                      "one member there" % (self.n_models, n_ghost))
+        if members and self.n_models == 1:
+            raise ValueError("DescriptorMLP: total_forces(members=True) is a committee's (n_models > 1)")
         B, NN = self._check(x)
         index = self._slot_index(index, x)
         own = None
@@ -609,6 +705,26 @@ class DescriptorMLP:
         e = torch.empty((B,), dtype=torch.float32, device=x.device)
         act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
         launches, rows = self._launches(species, x)
+        if self.n_models > 1:   # include/htf_committee.h: the two sweeps for all members at once
+            M = self.n_models
+            g = torch.empty((B, M, self.D), dtype=torch.float32, device=x.device)
+            e = torch.empty((B, M), dtype=torch.float32, device=x.device)
+            dev = torch.empty((B, 2), dtype=torch.float32, device=x.device)
+            mem = torch.empty((M, B, 4), dtype=torch.float32, device=x.device) if members else None
+            for _, d_rows, n_rows, d_w in launches:   # pass 1: every row is in exactly one list
+                check(lib.htf_cmt_grad(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, d_w,
+                                       self.mu.data_ptr(), float(self.gap), g.data_ptr(), e.data_ptr(), d_rows, n_rows,
+                                       float(self.r_cut or 0.0), M, self.n_species * self.P, ops._stream(x)))
+            check(lib.htf_cmt_forces(x.data_ptr(), ops._dt(x), index.data_ptr(), own.data_ptr() if own is not None else None, B,
+                                     NN, self.K, self.n_types, self.mu.data_ptr(), float(self.gap), g.data_ptr(), e.data_ptr(),
+                                     out.data_ptr(), ops._dt(out), v.data_ptr() if v is not None else None,
+                                     float(self.r_cut or 0.0), M, dev.data_ptr(), mem.data_ptr() if members else None,
+                                     ops._stream(x)))
+            self.deviation = dev
+            res = (out, v) if virial else (out,)
+            if members:
+                res = res + (mem,)
+            return res if len(res) > 1 else out
         if self.l_max:   # include/htf_angular.h: the table {g, p, S} per row and channel in place of g
             h = torch.empty((B + n_ghost, self.Dr, 4 if self.l_max == 1 else 10), dtype=torch.float32, device=x.device)
             for _, d_rows, n_rows, d_w in launches:
@@ -654,6 +770,7 @@ class DescriptorMLP:
         ``forces``) ``accum`` is [S, 1 + P]: row ``s`` holds the residuals and the gradient of network ``s`` over species
         ``s``'s rows, zeros when it has none; each row steps its own slice of ``w``."""
         self._no_angular("loss_gradient")
+        self._no_committee("loss_gradient")
         B, NN = self._check(x)
         pred, accum, launches, rows, scratch = self._sweep_buffers(x, labels, pred, accum, species,
                                                                    lambda: self.forces(x, species=species))
@@ -715,6 +832,7 @@ class DescriptorMLP:
         ``halo(rho)`` fills the ghosts' rows with their owners' residuals, and ``pred``, when not given, is ``total_forces``
         with the same ``n_ghost`` and ``halo``.  ``accum`` then holds this domain's rows' share: the sum over the domains is the
         whole system's sweep."""
+        self._no_committee("total_loss_gradient")
         if self.l_max:
             raise NotImplementedError("DescriptorMLP: total_loss_gradient() is the sweep of an l_max = 0 layer; with l_max = %d its "
                                       "follow-up angular_loss_gradient(x, labels, index) is the force-matching sweep" % self.l_max)
@@ -728,6 +846,7 @@ class DescriptorMLP:
         weights, evaluated here when not given; the residual is formed in fp32 with torch; a slot whose index is outside
         ``[0, B)`` has no reverse term.  Two calls on the same inputs give the same bits.  Callable on any layer with
         ``l_max > 0``, trainable or not; with ``l_max = 0`` it raises.  ``n_ghost`` and ``halo`` as for ``total_loss_gradient``."""
+        self._no_committee("angular_loss_gradient")
         if not self.l_max:
             raise ValueError("DescriptorMLP: angular_loss_gradient() is the sweep of the angular channels (l_max = 1 or 2); "
                              "total_loss_gradient(x, labels, index) is the sweep of this l_max = 0 layer")
@@ -777,6 +896,7 @@ class DescriptorMLP:
     def descriptor(self, nlist):
         """The network input [B, D] alone (the kernel's first stage), in the dtype of the pair-vector tensor: G, or
         [G | A | Q] with ``l_max > 0``."""
+        self._no_committee("descriptor")
         x = simmodel._as_nlist(nlist).tensor
         B, NN = self._check(x)
         out = torch.empty((B, self.D), dtype=x.dtype, device=x.device)

@@ -1722,6 +1722,10 @@ def compute_nlist_forces(nlist, energy, virial=False):
                          ' Did you put them in wrong order?')
     if isinstance(energy, DescriptorEnergy):
         training = getattr(_trace, "training_graph", False)
+        if training and getattr(energy.layer, "n_models", 1) > 1:
+            raise NotImplementedError("a DescriptorMLP committee (n_models = %d) is not trained by tfcompute(train=True) or "
+                                      "train_on_batch: layer.member(m, trainable=\"total\") is a view of member m that "
+                                      "total_loss_gradient and ops.optimizer_step train offline" % energy.layer.n_models)
         if training and not energy.layer.trainable:
             raise NotImplementedError("this DescriptorMLP is not trainable: neither tfcompute(train=True) nor train_on_batch "
                                       "covers a model that holds it (construct it with trainable=True)")

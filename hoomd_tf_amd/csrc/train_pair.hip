@@ -370,8 +370,8 @@ __global__ void optimizer_kernel(float *__restrict__ theta, unsigned P, const fl
                                  float *__restrict__ st, htf_optimizer_desc d) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     float *m = st, *v = st + 8;
+    float m_sched = st[16] == 0.0f ? 1.0f : st[17]; // first step by the counter: a stored 0 is an underflowed product, as in Keras
     float t = st[16] + 1.0f;
-    float m_sched = st[17] == 0.0f ? 1.0f : st[17];
     const float loss = accum[0] * scale;
     st[18] += loss;
     st[19] += 1.0f;
@@ -418,8 +418,8 @@ __global__ void optimizer_vec_kernel(float *__restrict__ theta, unsigned P, cons
     const unsigned k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= P) return;
     float *m = st + HTF_OPT_STATE_FLOATS, *v = m + P;
+    const float m_sched = st[16] == 0.0f ? 1.0f : st[17];
     const float t = st[16] + 1.0f;
-    const float m_sched = st[17] == 0.0f ? 1.0f : st[17];
     const float b1 = d.beta1, b2 = d.beta2;
     const float g = accum[1 + k] * scale;
     float th = theta[k];
@@ -450,8 +450,8 @@ __global__ void optimizer_vec_kernel(float *__restrict__ theta, unsigned P, cons
 __global__ void optimizer_vec_finish_kernel(const float *__restrict__ accum, float scale, float *__restrict__ st,
                                             htf_optimizer_desc d) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const float m_sched = st[16] == 0.0f ? 1.0f : st[17];
     const float t = st[16] + 1.0f;
-    const float m_sched = st[17] == 0.0f ? 1.0f : st[17];
     const float loss = accum[0] * scale;
     st[18] += loss;
     st[19] += 1.0f;

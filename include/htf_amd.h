@@ -282,7 +282,8 @@ typedef struct htf_optimizer_desc {
 
 /* One optimizer step ON THE DEVICE: grad_k = scale * d_accum[1 + k] + l1_reg[k]; loss = scale *
  * d_accum[0] is added to the running metric in d_state.  d_state: HTF_OPT_STATE_FLOATS floats,
- * zero-initialised by the caller (m_schedule is set to 1 on the first step). */
+ * zero-initialised by the caller.  The first step is the one that finds t == 0: it starts Nadam's m_schedule (the product of
+ * the u_t) from 1.  A stored m_schedule of 0 is the product underflowed, as in Keras (1 - 0 = 1 is then the correction). */
 HTF_API int htf_optimizer_step(float *d_theta, unsigned P, const float *d_accum, float scale,
                        float *d_state, const htf_optimizer_desc *desc, htf_stream stream);
 

@@ -13,7 +13,9 @@ forces, ``DescriptorMLP(conservative=True, l_max=1 or 2)``: include/htf_angular.
 trainable="angular")`` and ``angular_loss_gradient``: include/htf_atrain.h; the same forces and sweeps on one slab domain's
 rows, with the ghost particles' table rows from their owners: include/htf_cghost.h; a committee of M such networks,
 ``DescriptorMLP(conservative=True, n_models=M)``, whose ``total_forces`` gives the mean-model forces and leaves the per-particle
-model deviation in ``layer.deviation``, the descriptor and every exponential formed once for all members: include/htf_committee.h).
+model deviation in ``layer.deviation``, the descriptor and every exponential formed once for all members: include/htf_committee.h;
+``trainable="committee"`` trains that committee where it runs, ``committee_loss_gradient`` being the force-matching sweep of all
+M members at once, one wave per member on the same rows: include/htf_cmt_train.h).
 The offline path ``iter_from_trajectory`` / ``ArrayTrajectory`` runs a
 ``SimModel`` over stored frames.
 """

@@ -320,10 +320,17 @@ CMT_PROTOTYPES = {
     "htf_cmt_forces": (_i, CF_PROTOTYPES["htf_cf_forces"][1][:-1] + [_u, _vp, _vp, _vp]),
 }
 
+# force matching for every member of a committee in one sweep (include/htf_cmt_train.h; DescriptorMLP.committee_loss_gradient):
+# htf_ct_loss_grad's arguments with ``unsigned n_models, unsigned weight_stride, unsigned accum_stride`` before the stream
+CMT_TRAIN_PROTOTYPES = {
+    "htf_cmt_scratch_floats": (C.c_size_t, [_u, _u, _u, _u, _u, _u]),
+    "htf_cmt_loss_grad": (_i, CT_PROTOTYPES["htf_ct_loss_grad"][1][:-1] + [_u, _u, _u, _vp]),
+}
+
 # every table above: what the ctypes and the pybind11 binding both declare
 ALL_PROTOTYPES = tuple((name, proto) for table in (PROTOTYPES, STANDIN_PROTOTYPES, STEP_CHECK_PROTOTYPES, CG_PROTOTYPES, GEOM_PROTOTYPES, NLIST_PROTOTYPES,
                                                    BP_PROTOTYPES, CF_PROTOTYPES, CT_PROTOTYPES, ANG_PROTOTYPES, AT_PROTOTYPES, CGHOST_PROTOTYPES,
-                                                   CMT_PROTOTYPES)
+                                                   CMT_PROTOTYPES, CMT_TRAIN_PROTOTYPES)
                        for name, proto in table.items())
 
 

@@ -20,6 +20,7 @@
 #include "htf_bp.h"
 #include "htf_cforce.h"
 #include "htf_committee.h"
+#include "htf_cmt_train.h"
 #include "htf_angular.h"
 #include "htf_ctrain.h"
 #include "htf_atrain.h"
@@ -223,6 +224,11 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
     X(htf_cmt_grad) \
     X(htf_cmt_forces)
 
+// include/htf_cmt_train.h: force matching for every member of a committee in one sweep (_lib.CMT_TRAIN_PROTOTYPES)
+#define HTF_CMT_TRAIN_FUNCTIONS(X) \
+    X(htf_cmt_scratch_floats) \
+    X(htf_cmt_loss_grad)
+
 PYBIND11_MODULE(_htf_abi, m) {
     m.doc() = "pybind11 binding of libhtf_amd.so's C ABI: pointers as integers";
     // a stale module (or library): this module's templates were instantiated from one header, the library it resolved at load
@@ -244,5 +250,6 @@ PYBIND11_MODULE(_htf_abi, m) {
     HTF_AT_FUNCTIONS(X)
     HTF_CGHOST_FUNCTIONS(X)
     HTF_CMT_FUNCTIONS(X)
+    HTF_CMT_TRAIN_FUNCTIONS(X)
 #undef X
 }

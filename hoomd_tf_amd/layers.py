@@ -380,10 +380,20 @@ class DescriptorMLP:
     + 1`` floats, rounded up to a multiple of 4, K4 likewise); a committee above 160 KiB raises at construction.
     ``layer.member(m)`` is a plain ``DescriptorMLP`` whose ``w`` is a view of member ``m``'s slice: ``forces``,
     ``total_forces``, ``descriptor``, ``total_loss_gradient`` and ``ops.optimizer_step`` on it evaluate and train that member in
-    place, and the committee sees the new weights at its next call -- this is how a committee is trained, offline.  Not
-    covered, each raises: angular channels (``l_max > 0``), ``trainable`` on the committee itself and
-    ``tfcompute(train=True)``, slab or brick domains (``n_ghost > 0``), and the row-operator and sweep methods, which point to
-    ``member(m)``.  ``n_models=1`` is the layer without the argument.
+    place, and the committee sees the new weights at its next call -- one member at a time, offline.  Not covered, each
+    raises: angular channels (``l_max > 0``), ``trainable=True``, ``"total"`` or ``"angular"`` on the committee itself, slab or
+    brick domains (``n_ghost > 0``), and the row-operator and single-network sweep methods, which point to ``member(m)``.
+    ``n_models=1`` is the layer without the argument.
+
+    ``trainable="committee"`` (with ``n_models >= 2`` and ``l_max = 0``; htf_cmt_loss_grad, include/htf_cmt_train.h) trains the
+    committee where it runs and implies ``conservative=True``: every member is fitted on its own to the same labels, the loss
+    being ``sum_m SSR^m``.  ``committee_loss_gradient(x, labels, index)`` is ``total_loss_gradient`` for all members in one
+    sweep -- one wave per member on the same rows, the waves sharing the exponentials and the descriptor --
+    and returns ``accum`` [M, 1 + P]; it is callable on any committee.  Under ``tfcompute.attach(..., train=True)`` every step
+    is that sweep on the step's own list, index and members' forces, and M optimizer steps, member ``m`` on its slice of ``w``
+    with its own optimizer state; the loss metric reads the mean of the members' losses.  The sweep keeps all M networks and
+    six exchange lines and 256 slot terms per member in LDS, ``4 (M (P4 + 640) + K4)`` bytes; above 160 KiB the constructor raises.  In the run,
+    ``n_species > 1``, several ranks and batches raise; offline the method covers species.
     Limits: ``n_types * K * (1 + l_max) <= 64``, ``H1, H2 <= 64``, at most 256 neighbor slots."""
 
     name = 'descriptor-mlp'
@@ -405,12 +415,21 @@ class DescriptorMLP:
             raise ValueError("DescriptorMLP: n_models must be an integer in [1, %d], not %r: a larger committee is several "
                              "layers, each evaluated with its own total_forces" % (self.MAX_MODELS, n_models))
         self.n_models = n_models = int(n_models)
+        committee = isinstance(trainable, str) and trainable == "committee"
+        if committee:
+            if n_models < 2:
+                raise ValueError("DescriptorMLP: trainable=\"committee\" trains the members of a committee and needs n_models >= 2, "
+                                 "not n_models = %d; trainable=\"total\" fits one network" % n_models)
+            if l_max:
+                raise ValueError("DescriptorMLP: trainable=\"committee\" needs l_max = 0, not l_max = %d: the committee's sweeps "
+                                 "have no angular form" % l_max)
+            conservative = True   # the forces of the total energy, fitted and run alike
         if n_models > 1:
             if l_max:
                 raise NotImplementedError("DescriptorMLP: n_models = %d does not go with l_max = %d: a committee of angular "
                                           "networks is a follow-up; M layers of l_max = %d, one total_forces each, evaluate it"
                                           % (n_models, l_max, l_max))
-            if trainable is not False:
+            if trainable is not False and not committee:
                 raise NotImplementedError("DescriptorMLP: n_models = %d does not go with trainable=%r: training a committee in "
                                           "the running simulation is a follow-up; member(m, trainable=\"total\") is a view of "
                                           "member m that total_loss_gradient and ops.optimizer_step train in place"
@@ -419,8 +438,9 @@ class DescriptorMLP:
                 raise ValueError("DescriptorMLP: n_models = %d needs conservative=True: the deviation is defined on the forces "
                                  "of the total energy (total_forces)" % n_models)
         if isinstance(trainable, str):
-            if trainable not in ("total", "angular"):
-                raise ValueError("DescriptorMLP: trainable must be False, True, 'total' or 'angular', not %r" % (trainable,))
+            if trainable not in ("total", "angular", "committee"):
+                raise ValueError("DescriptorMLP: trainable must be False, True, 'total', 'angular' or 'committee', not %r"
+                                 % (trainable,))
             if trainable == "angular" and not l_max:
                 raise ValueError("DescriptorMLP: trainable=\"angular\" fits the angular channels and needs l_max = 1 or 2; "
                                  "trainable=\"total\" fits the conservative forces of an l_max = 0 layer")
@@ -471,6 +491,12 @@ class DescriptorMLP:
                 raise ValueError("DescriptorMLP: a committee of %d networks of %d x %d x %d needs %d bytes of LDS for its first "
                                  "sweep, above the %d bytes of one compute unit: fewer members, or narrower networks"
                                  % (n_models, self.D, H1, H2, need, self.MAX_COMMITTEE_LDS))
+            need = self.committee_train_lds_bytes(n_models, K, n_types, H1, H2)
+            if committee and need > self.MAX_COMMITTEE_LDS:
+                raise ValueError("DescriptorMLP: the training sweep of a committee of %d networks of %d x %d x %d needs %d bytes "
+                                 "of LDS, above the %d bytes of one compute unit: fewer members, or narrower networks; "
+                                 "member(m, trainable=\"total\") trains one member at a time"
+                                 % (n_models, self.D, H1, H2, need, self.MAX_COMMITTEE_LDS))
         ps = [mlp_params(seed=seed + s, K=self.D, H1=H1, H2=H2) for s in range(n_models * n_species)]   # [M][S]
         self._shapes = [ps[0][k].shape for k in self._KEYS]
         self.P = sum(int(np.prod(sh)) for sh in self._shapes)   # floats of one network
@@ -484,6 +510,14 @@ class DescriptorMLP:
         D = K * n_types
         member = (D * (H1 + 1) + H1 + H1 * (H2 + 1) + H2 + H2 + 1 + 3) & ~3
         return 4 * (n_models * member + ((K + 3) & ~3) + 16 * 64)
+
+    @staticmethod
+    def committee_train_lds_bytes(n_models, K, n_types, H1, H2):
+        """Dynamic LDS of the committee's training sweep (htf_cmt_loss_grad): per member the network with rows padded by one
+        float, six exchange lines and one row of 256 slot terms; and the centres."""
+        D = K * n_types
+        member = (D * (H1 + 1) + H1 + H1 * (H2 + 1) + H2 + H2 + 1 + 3) & ~3
+        return 4 * (n_models * (member + 6 * 64 + 256) + ((K + 3) & ~3))
 
     def member(self, m, trainable=False):
         """Member ``m`` of a committee as a plain ``DescriptorMLP`` of the same configuration (``n_models=1``, ``trainable`` as
@@ -511,7 +545,7 @@ class DescriptorMLP:
         cfg = {'K': self.K, 'H1': self.H1, 'H2': self.H2, 'low': self.low, 'high': self.high, 'n_types': self.n_types,
                'activation': self.activation}
         if self.trainable:
-            cfg['trainable'] = self.trainable   # (True, "total" or "angular")
+            cfg['trainable'] = self.trainable   # (True, "total", "angular" or "committee")
         if self.r_cut is not None:
             cfg['r_cut'] = self.r_cut
         if self.n_species != 1:
@@ -891,6 +925,57 @@ class DescriptorMLP:
                                        act, d_w, self.mu.data_ptr(), float(self.gap), rho.data_ptr(),
                                        accum.data_ptr() + 4 * s * (1 + P), scratch.data_ptr(), d_rows, n_rows,
                                        float(self.r_cut or 0.0), ops._stream(x)))
+        return accum
+
+    def committee_loss_gradient(self, x, labels, index, types=None, pred=None, accum=None, species=None):
+        """``total_loss_gradient`` for every member of a committee in one sweep (htf_cmt_loss_grad, include/htf_cmt_train.h):
+        returns ``accum`` [M, 1 + P] fp32 on the device -- [M, S, 1 + P] with ``n_species = S > 1``, zero rows for an absent
+        species -- whose row ``m`` holds {SSR^m, d SSR^m / d theta^m} for the residuals of member ``m``'s forces against
+        ``labels`` [B, 4]: what ``member(m, trainable="total").total_loss_gradient(x, labels, index, pred=pred[m])`` returns,
+        without reading the pair vectors, the index and the neighbors' residuals M times.  Every member is fitted on its own to
+        the same labels; ``ops.optimizer_step(w[m P:(m + 1) P], accum[m], 1 / (4 B), ...)`` steps member ``m``.  ``pred``
+        [M, B, 4] fp32: the members tensor of ``total_forces(x, index, ..., members=True)`` at the current weights, evaluated
+        here (with ``types``) when not given.  The residual table [B, M, 4] is formed in fp32 with torch and every row's is
+        read: ``x`` holds the whole system.  Two calls on the same inputs give the same bits, and row ``m`` depends on member
+        ``m``'s weights and residuals alone.  Callable on any committee, trainable or not; a single network raises."""
+        if self.n_models < 2:
+            raise ValueError("DescriptorMLP: committee_loss_gradient() is a committee's (n_models > 1); "
+                             "total_loss_gradient(x, labels, index) is the sweep of this single network")
+        B, NN = self._check(x)
+        index = self._slot_index(index, x)
+        M, S, P = self.n_models, self.n_species, self.P
+        ops._dev(labels, "labels")
+        ops._dt(labels)
+        if tuple(labels.shape) != (B, 4) or labels.device != x.device:
+            raise ValueError("DescriptorMLP: labels must be [%d, 4] on %s, got %s on %s" % (B, x.device, tuple(labels.shape), labels.device))
+        if pred is None:
+            pred = self.total_forces(x, index, types=types, species=species, members=True)[-1]
+        ops._dev(pred, "pred", torch.float32)
+        if tuple(pred.shape) != (M, B, 4) or pred.device != x.device:
+            raise ValueError("DescriptorMLP: pred must be [%d, %d, 4] on %s (total_forces(..., members=True)), got %s on %s"
+                             % (M, B, x.device, tuple(pred.shape), pred.device))
+        if accum is None:
+            accum = torch.empty((M, S, 1 + P) if S > 1 else (M, 1 + P), dtype=torch.float32, device=x.device)
+        ops._dev(accum, "accum", torch.float32)
+        if accum.numel() != M * S * (1 + P) or accum.device != x.device or not accum.is_contiguous():
+            raise ValueError("DescriptorMLP: accum must hold %d contiguous floats on %s" % (M * S * (1 + P), x.device))
+        launches, rows = self._launches(species, x)
+        # one scratch buffer for the largest species: the launches run one after the other on the stream
+        scratch = torch.empty(max(1, int(lib.htf_cmt_scratch_floats(max([n for _, _, n, _ in launches] or [0]), self.K,
+                                                                    self.n_types, self.H1, self.H2, M))),
+                              dtype=torch.float32, device=x.device)
+        present = {s for s, _, _, _ in launches}   # (every other row of accum is written by its species' launch)
+        for s in range(S):
+            if s not in present:
+                accum.view(M, S, 1 + P)[:, s].zero_()
+        # [B][M][4]: a particle's residuals are one record of 16 M bytes
+        rho = (pred.detach() - labels.detach().to(torch.float32).unsqueeze(0)).permute(1, 0, 2).contiguous()
+        act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
+        for s, d_rows, n_rows, d_w in launches:   # (d_w: species s of member 0; members S P floats apart)
+            check(lib.htf_cmt_loss_grad(x.data_ptr(), ops._dt(x), index.data_ptr(), B, NN, self.K, self.n_types, self.H1, self.H2,
+                                        act, d_w, self.mu.data_ptr(), float(self.gap), rho.data_ptr(),
+                                        accum.data_ptr() + 4 * s * (1 + P), scratch.data_ptr(), d_rows, n_rows,
+                                        float(self.r_cut or 0.0), M, S * P, S * (1 + P), ops._stream(x)))
         return accum
 
     def descriptor(self, nlist):

@@ -1722,7 +1722,8 @@ def compute_nlist_forces(nlist, energy, virial=False):
                          ' Did you put them in wrong order?')
     if isinstance(energy, DescriptorEnergy):
         training = getattr(_trace, "training_graph", False)
-        if training and getattr(energy.layer, "n_models", 1) > 1:
+        cmt_train = training and getattr(energy.layer, "trainable", False) == "committee"
+        if training and getattr(energy.layer, "n_models", 1) > 1 and not cmt_train:
             raise NotImplementedError("a DescriptorMLP committee (n_models = %d) is not trained by tfcompute(train=True) or "
                                       "train_on_batch: layer.member(m, trainable=\"total\") is a view of member m that "
                                       "total_loss_gradient and ops.optimizer_step train offline" % energy.layer.n_models)
@@ -1743,7 +1744,14 @@ def compute_nlist_forces(nlist, energy, virial=False):
             types = _unwrap(energy.positions)[:nl.tensor.shape[0]] if lay.n_types > 1 else None
             # (a slab's list also names ghost particles: their rows of the gathered table come from their owners)
             n_ghost, halo = (nl if nl.index is not None else energy.nlist).ghost or (0, None)
-            out = lay.total_forces(nl.tensor, index, virial, types=types, species=energy.species, n_ghost=n_ghost, halo=halo)
+            members = None
+            if cmt_train:
+                # (a trainable committee: the members' own forces are the prediction its sweep is handed)
+                out = lay.total_forces(nl.tensor, index, virial, types=types, species=energy.species, n_ghost=n_ghost, halo=halo,
+                                       members=True)
+                out, members = (out[:-1] if virial else out[0]), out[-1]
+            else:
+                out = lay.total_forces(nl.tensor, index, virial, types=types, species=energy.species, n_ghost=n_ghost, halo=halo)
         else:
             out = lay.forces(nl.tensor, virial, species=energy.species)
         entry = {"op": "descriptor_mlp", "species": energy.species}   # (no plan: a model calling it keeps the eager path)
@@ -1753,6 +1761,8 @@ def compute_nlist_forces(nlist, energy, virial=False):
             entry.update(layer=energy.layer, nlist=nl, forces=out[0] if virial else out, index=index, types=types)
             if getattr(lay, "conservative", False):
                 entry.update(n_ghost=n_ghost, halo=halo)
+                if members is not None:
+                    entry.update(members=members)
         _trace_log().append(entry)
         return out
     if isinstance(energy, BiasedEnergy):

@@ -431,6 +431,8 @@ class tfcompute:
         theta = layer.w
         if getattr(self, "_opt_desc", None) is None:
             self._opt_desc = m.optimizer.desc(layer.nonneg_mask, layer.l1_reg)
+        if layer.trainable == "committee":
+            return self._train_descriptor_committee(nlist_t, offset, n, layer, entry, ranks)
         pred = entry["forces"]
         pred = pred if pred.dtype == torch.float32 else pred.to(torch.float32)
         S = getattr(layer, "n_species", 1)
@@ -481,6 +483,39 @@ class tfcompute:
             if c:
                 ops.optimizer_step(layer.w[s * P:(s + 1) * P], accum[s], scale, self._opt_states[s], self._opt_desc)
         loss = accum[:, 0].sum() * scale
+        self._opt_state[20] = loss      # (last loss, running sum and count: what the loss metric reads)
+        self._opt_state[18] += loss
+        self._opt_state[19] += 1.0
+
+    def _train_descriptor_committee(self, nlist_t, offset, n, layer, entry, ranks):
+        """A committee (trainable="committee"): one sweep for all members (DescriptorMLP.committee_loss_gradient, handed the
+        members' forces the step has just evaluated), then one optimizer step per member on that member's slice of the weights,
+        each with its own optimizer state and the scale 1 / (4 n): every member is fitted on its own to the same labels.  The
+        reported loss is the mean of the members' losses."""
+        m, M, P = self.model, layer.n_models, layer.P
+        if getattr(layer, "n_species", 1) > 1:
+            raise NotImplementedError("training a DescriptorMLP committee with n_species = %d in the running simulation is not "
+                                      "implemented: committee_loss_gradient(..., species=...) covers species offline"
+                                      % layer.n_species)
+        if ranks:
+            raise NotImplementedError("training a DescriptorMLP committee over several ranks is not implemented: a committee "
+                                      "does not run on a domain's rows")
+        if self.batch_size:
+            raise NotImplementedError("training a DescriptorMLP committee in batches (batch_size = %d) is not implemented: the "
+                                      "sweep gathers the residuals of the whole system; batch_size = 0 takes the rows in one"
+                                      % self.batch_size)
+        if getattr(self, "_opt_states", None) is None:
+            self._opt_states = [torch.zeros(ops.optimizer_state_floats(P), dtype=torch.float32, device=self.system.device)
+                                for _ in range(M)]
+            self._opt_state = torch.zeros(_lib.OPT_STATE_FLOATS, dtype=torch.float32, device=self.system.device)  # the metric's
+            if m.metrics:
+                m.metrics[0].state = self._opt_state
+        accum = layer.committee_loss_gradient(nlist_t, self._labels[offset:offset + n], entry["index"], types=entry.get("types"),
+                                              pred=entry["members"])
+        scale = 1.0 / (4.0 * float(n))
+        for k in range(M):
+            ops.optimizer_step(layer.w[k * P:(k + 1) * P], accum[k], scale, self._opt_states[k], self._opt_desc)
+        loss = accum[:, 0].mean() * scale
         self._opt_state[20] = loss      # (last loss, running sum and count: what the loss metric reads)
         self._opt_state[18] += loss
         self._opt_state[19] += 1.0

@@ -203,6 +203,16 @@ enum {
     HTFS_BF_HALO_TIMEOUT = 32   /* transport "peer": a neighbor's message did not arrive within the spin limit */
 };
 
+/* A FLAGGED plan (tests/test_gpu_brick_kernels.py test_overflows): the kernels clamp and carry on, and store nothing outside their
+ * arrays.  MIG_OVERFLOW: the header count is min(n, mig_cap[m] - 1), the first so many migrants of the message travel, the others
+ * are in no message and no candidate list.  INT / BND_OVERFLOW: N_INT / N_BND are clamped to the capacity and the first cap_int /
+ * cap_bnd rows of the class-sorted candidates are placed; CLASS[] and N_CAND keep the unclamped boundaries, so after a BND_OVERFLOW
+ * the halo pack reads up to pos[cap_int + n_bnd - 1], past the local rows (the caller's array has the ghost region there).
+ * GHOST_OVERFLOW: MSG[m] is clamped to ghost_cap[m], the message is its first ghost_cap[m] rows in class order, the rows cut off
+ * have 0xFFFFFFFF in htfs_brick_row_slots.  LOST: the row's destination key is 0 -- it stays a candidate of this brick.
+ * A rebuild writes N_INT, N_BND, N_CAND, MSG[0 .. n_msg), CLASS[0 .. 4^ndim] and all of SLOT, adds to N_ARRIVED and REBUILDS, ORs
+ * into FLAGS, and leaves every other word of d_counts alone. */
+
 /* scratch of a rebuild, all caller-owned: cand = cap_int + cap_bnd + sum_m mig_cap[m] candidate slots */
 typedef struct htfs_brick_work {
     unsigned *key;          /* [cand] */

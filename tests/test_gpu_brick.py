@@ -92,6 +92,9 @@ def test_brick_kernels_match_torch(htf, cuda, grid, dtype):
                 assert ck[w] == ct[w], w
             assert np.array_equal(ck[_lib.BC_MSG:_lib.BC_MSG + 8], ct[_lib.BC_MSG:_lib.BC_MSG + 8])
             assert np.array_equal(ck[_lib.BC_CLASS:_lib.BC_CLASS + 17], ct[_lib.BC_CLASS:_lib.BC_CLASS + 17])
+            assert ck[_lib.BC_FLAGS] == ct[_lib.BC_FLAGS] == 0
+            slots = slice(_lib.BC_SLOT, _lib.BC_SLOT + 16 * _lib.BRICK_MAX_MSG)   # where class c starts in message m, -1: not carried
+            assert np.array_equal(ck[slots], ct[slots])
 
 
 @pytest.mark.parametrize("local_grid", [True, False])

@@ -18,6 +18,10 @@ model deviation in ``layer.deviation``, the descriptor and every exponential for
 M members at once, one wave per member on the same rows: include/htf_cmt_train.h).
 The offline path ``iter_from_trajectory`` / ``ArrayTrajectory`` runs a
 ``SimModel`` over stored frames.
+``DeviationSelector`` consumes the committee's deviation where it is produced: ``sel.update(layer.deviation, positions, box)``
+classifies the frame by its largest deviation (accurate, candidate, failed: the DP-GEN rule) and keeps the candidates'
+positions and box in a fixed-capacity device buffer, in three launches and without a read-back; ``sel.trajectory()`` hands
+them to ``iter_from_trajectory`` for labelling and offline training (include/htf_select.h).
 """
 from . import _lib
 from ._lib import NlistOverflowError, SkewedBoxError
@@ -35,5 +39,6 @@ from .cgmap import sparse_mapping, center_of_mass, compute_nlist
 from .molgeom import mol_bond_distance, mol_angle, mol_dihedral, mol_features_multiple
 from .tensorflowcompute import tfcompute
 from .trajectory import ArrayTrajectory, iter_from_trajectory
+from .select import DeviationSelector
 
 __version__ = "0.1.0"

@@ -327,10 +327,21 @@ CMT_TRAIN_PROTOTYPES = {
     "htf_cmt_loss_grad": (_i, CT_PROTOTYPES["htf_ct_loss_grad"][1][:-1] + [_u, _u, _u, _vp]),
 }
 
+# frame selection by committee deviation (include/htf_select.h; hoomd_tf_amd/select.py DeviationSelector)
+SEL_FIRST, SEL_LARGEST = 0, 1
+SEL_FORCE, SEL_ENERGY = 0, 1
+SEL_SEEN, SEL_ACCURATE, SEL_CANDIDATE, SEL_FAILED, SEL_STORED, SEL_DROPPED, SEL_REPLACED, SEL_SLOT, SEL_LAST, SEL_HEADER_WORDS = 0, 1, 2, 3, 4, 5, 6, 7, 8, 16
+SEL_MAX_CAPACITY, SEL_MAX_BLOCKS = 65536, 1024
+SEL_PROTOTYPES = {
+    "htf_sel_state_words": (C.c_ulonglong, [_u]),
+    "htf_sel_update": (_i, [_vp, _u, _i, C.c_float, C.c_float, _i, _u, _vp, _vp, _vp, _i, _vp, _vp, _u, _vp]),
+    "htf_sel_reset": (_i, [_vp, _u, _vp]),
+}
+
 # every table above: what the ctypes and the pybind11 binding both declare
 ALL_PROTOTYPES = tuple((name, proto) for table in (PROTOTYPES, STANDIN_PROTOTYPES, STEP_CHECK_PROTOTYPES, CG_PROTOTYPES, GEOM_PROTOTYPES, NLIST_PROTOTYPES,
                                                    BP_PROTOTYPES, CF_PROTOTYPES, CT_PROTOTYPES, ANG_PROTOTYPES, AT_PROTOTYPES, CGHOST_PROTOTYPES,
-                                                   CMT_PROTOTYPES, CMT_TRAIN_PROTOTYPES)
+                                                   CMT_PROTOTYPES, CMT_TRAIN_PROTOTYPES, SEL_PROTOTYPES)
                        for name, proto in table.items())
 
 

@@ -25,6 +25,7 @@
 #include "htf_ctrain.h"
 #include "htf_atrain.h"
 #include "htf_cghost.h"
+#include "htf_select.h"
 
 namespace py = pybind11;
 
@@ -229,6 +230,12 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
     X(htf_cmt_scratch_floats) \
     X(htf_cmt_loss_grad)
 
+// include/htf_select.h: frame selection by committee deviation (_lib.SEL_PROTOTYPES)
+#define HTF_SEL_FUNCTIONS(X) \
+    X(htf_sel_state_words) \
+    X(htf_sel_update) \
+    X(htf_sel_reset)
+
 PYBIND11_MODULE(_htf_abi, m) {
     m.doc() = "pybind11 binding of libhtf_amd.so's C ABI: pointers as integers";
     // a stale module (or library): this module's templates were instantiated from one header, the library it resolved at load
@@ -251,5 +258,6 @@ PYBIND11_MODULE(_htf_abi, m) {
     HTF_CGHOST_FUNCTIONS(X)
     HTF_CMT_FUNCTIONS(X)
     HTF_CMT_TRAIN_FUNCTIONS(X)
+    HTF_SEL_FUNCTIONS(X)
 #undef X
 }

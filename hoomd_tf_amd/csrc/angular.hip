@@ -428,25 +428,12 @@ extern "C" int htf_ang_grad(const void *d_nlist, int nlist_dtype, unsigned B, un
     if (n_rows == 0) return HTF_OK;
     const size_t lds = desc_lds_forces(K, n_types * (1 + l_max), H1, H2);   // (the weights of D = K n_types (1 + l_max) inputs)
     const hipStream_t s = (hipStream_t)stream;
-#define HTF_AG(TANH, CUT, LM, T, V4)                                                                                                 \
-    hipLaunchKernelGGL((ang_grad_kernel<TANH, CUT, LM, T>), dim3(desc_grid(n_rows)), dim3(256), lds, s, (const V4 *)d_nlist, d_rows,   \
-                       n_rows, NN, d_weights, d_mu, (int)K, (int)n_types, (int)H1, (int)H2, gap, r_cut, d_table, d_energy)
-#define HTF_AG1(TANH, CUT, LM)                                                                                                       \
-    do {                                                                                                                             \
-        if (nlist_dtype == HTF_F32) HTF_AG(TANH, CUT, LM, float, float4); else HTF_AG(TANH, CUT, LM, double, double4);               \
-    } while (0)
-#define HTF_AG2(TANH, CUT)                                                                                                           \
-    do {                                                                                                                             \
-        if (l_max == 1) HTF_AG1(TANH, CUT, 1); else HTF_AG1(TANH, CUT, 2);                                                           \
-    } while (0)
-    if (activation == HTF_ACT_TANH) {
-        if (r_cut > 0.0f) HTF_AG2(true, true); else HTF_AG2(true, false);
-    } else {
-        if (r_cut > 0.0f) HTF_AG2(false, true); else HTF_AG2(false, false);
-    }
-#undef HTF_AG2
-#undef HTF_AG1
-#undef HTF_AG
+    desc_dispatch([&](auto TANH, auto CUT, auto L2, auto F64) {
+        using IT = desc_in_t<F64>;
+        hipLaunchKernelGGL((ang_grad_kernel<TANH, CUT, L2 ? 2 : 1, IT>), dim3(desc_grid(n_rows)), dim3(256), lds, s,
+                           (const typename Vec4<IT>::type *)d_nlist, d_rows, n_rows, NN, d_weights, d_mu, (int)K, (int)n_types, (int)H1,
+                           (int)H2, gap, r_cut, d_table, d_energy);
+    }, activation == HTF_ACT_TANH, r_cut > 0.0f, l_max == 2, nlist_dtype == HTF_F64);
     return check_launch("ang_grad_kernel");
 }
 
@@ -466,25 +453,12 @@ extern "C" int htf_ang_forces_ghost(const void *d_nlist, int nlist_dtype, const 
     const size_t lds = ang_lds_forces(K);
     const int out_f64 = force_dtype == HTF_F64;
     const hipStream_t s = (hipStream_t)stream;
-#define HTF_AF(VIR, CUT, LM, T, V4)                                                                                                  \
-    hipLaunchKernelGGL((ang_force_kernel<VIR, CUT, LM, T>), dim3(desc_grid(B)), dim3(256), lds, s, (const V4 *)d_nlist, d_index,       \
-                       d_types, B, n_table, NN, d_mu, (int)K, (int)n_types, gap, r_cut, d_table, d_energy, d_force, out_f64, d_virial9)
-#define HTF_AF1(VIR, CUT, LM)                                                                                                        \
-    do {                                                                                                                             \
-        if (nlist_dtype == HTF_F32) HTF_AF(VIR, CUT, LM, float, float4); else HTF_AF(VIR, CUT, LM, double, double4);                 \
-    } while (0)
-#define HTF_AF2(VIR, CUT)                                                                                                            \
-    do {                                                                                                                             \
-        if (l_max == 1) HTF_AF1(VIR, CUT, 1); else HTF_AF1(VIR, CUT, 2);                                                             \
-    } while (0)
-    if (d_virial9) {
-        if (r_cut > 0.0f) HTF_AF2(true, true); else HTF_AF2(true, false);
-    } else {
-        if (r_cut > 0.0f) HTF_AF2(false, true); else HTF_AF2(false, false);
-    }
-#undef HTF_AF2
-#undef HTF_AF1
-#undef HTF_AF
+    desc_dispatch([&](auto VIR, auto CUT, auto L2, auto F64) {
+        using IT = desc_in_t<F64>;
+        hipLaunchKernelGGL((ang_force_kernel<VIR, CUT, L2 ? 2 : 1, IT>), dim3(desc_grid(B)), dim3(256), lds, s,
+                           (const typename Vec4<IT>::type *)d_nlist, d_index, d_types, B, n_table, NN, d_mu, (int)K, (int)n_types, gap,
+                           r_cut, d_table, d_energy, d_force, out_f64, d_virial9);
+    }, d_virial9 != nullptr, r_cut > 0.0f, l_max == 2, nlist_dtype == HTF_F64);
     return check_launch("ang_force_kernel");
 }
 
@@ -507,20 +481,10 @@ extern "C" int htf_ang_descriptor(const void *d_nlist, int nlist_dtype, unsigned
     const size_t lds = desc_lds_descriptor(K);
     const int out_f64 = out_dtype == HTF_F64;
     const hipStream_t s = (hipStream_t)stream;
-#define HTF_AD(CUT, LM, T, V4)                                                                                                       \
-    hipLaunchKernelGGL((ang_desc_kernel<CUT, LM, T>), dim3(desc_grid(B)), dim3(256), lds, s, (const V4 *)d_nlist, B, NN, d_mu, (int)K, \
-                       (int)n_types, gap, r_cut, d_out, out_f64)
-#define HTF_AD1(CUT, LM)                                                                                                             \
-    do {                                                                                                                             \
-        if (nlist_dtype == HTF_F32) HTF_AD(CUT, LM, float, float4); else HTF_AD(CUT, LM, double, double4);                           \
-    } while (0)
-#define HTF_AD2(CUT)                                                                                                                 \
-    do {                                                                                                                             \
-        if (l_max == 1) HTF_AD1(CUT, 1); else HTF_AD1(CUT, 2);                                                                       \
-    } while (0)
-    if (r_cut > 0.0f) HTF_AD2(true); else HTF_AD2(false);
-#undef HTF_AD2
-#undef HTF_AD1
-#undef HTF_AD
+    desc_dispatch([&](auto CUT, auto L2, auto F64) {
+        using IT = desc_in_t<F64>;
+        hipLaunchKernelGGL((ang_desc_kernel<CUT, L2 ? 2 : 1, IT>), dim3(desc_grid(B)), dim3(256), lds, s,
+                           (const typename Vec4<IT>::type *)d_nlist, B, NN, d_mu, (int)K, (int)n_types, gap, r_cut, d_out, out_f64);
+    }, r_cut > 0.0f, l_max == 2, nlist_dtype == HTF_F64);
     return check_launch("ang_desc_kernel");
 }

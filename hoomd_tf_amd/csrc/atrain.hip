@@ -311,31 +311,12 @@ extern "C" int htf_at_loss_grad_ghost(const void *d_nlist, int nlist_dtype, cons
     const hipStream_t s = (hipStream_t)stream;
     if (grid) {
         const size_t lds = dtrain_lds(K, Tw, H1, H2);
-#define HTF_AT(TANH, CUT, LIST, LM, T, V4)                                                                                             \
-    hipLaunchKernelGGL((at_sweep_kernel<TANH, CUT, LIST, LM, T>), dim3(grid), dim3(256), lds, s, (const V4 *)d_nlist, d_index, d_rows,  \
-                       n_rows, n_table, NN, d_weights, d_mu, (int)K, (int)n_types, (int)H1, (int)H2, gap, r_cut, (const float4 *)d_rho, \
-                       d_scratch)
-#define HTF_AT0(TANH, CUT, LIST, LM)                                                                                                   \
-    do {                                                                                                                               \
-        if (nlist_dtype == HTF_F32) HTF_AT(TANH, CUT, LIST, LM, float, float4); else HTF_AT(TANH, CUT, LIST, LM, double, double4);     \
-    } while (0)
-#define HTF_AT1(TANH, CUT, LIST)                                                                                                       \
-    do {                                                                                                                               \
-        if (l_max == 1) HTF_AT0(TANH, CUT, LIST, 1); else HTF_AT0(TANH, CUT, LIST, 2);                                                 \
-    } while (0)
-#define HTF_AT2(TANH, CUT)                                                                                                             \
-    do {                                                                                                                               \
-        if (d_rows) HTF_AT1(TANH, CUT, true); else HTF_AT1(TANH, CUT, false);                                                          \
-    } while (0)
-        if (activation == HTF_ACT_TANH) {
-            if (r_cut > 0.0f) HTF_AT2(true, true); else HTF_AT2(true, false);
-        } else {
-            if (r_cut > 0.0f) HTF_AT2(false, true); else HTF_AT2(false, false);
-        }
-#undef HTF_AT2
-#undef HTF_AT1
-#undef HTF_AT0
-#undef HTF_AT
+        desc_dispatch([&](auto TANH, auto CUT, auto LIST, auto L2, auto F64) {
+            using IT = desc_in_t<F64>;
+            hipLaunchKernelGGL((at_sweep_kernel<TANH, CUT, LIST, L2 ? 2 : 1, IT>), dim3(grid), dim3(256), lds, s,
+                               (const typename Vec4<IT>::type *)d_nlist, d_index, d_rows, n_rows, n_table, NN, d_weights, d_mu, (int)K,
+                               (int)n_types, (int)H1, (int)H2, gap, r_cut, (const float4 *)d_rho, d_scratch);
+        }, activation == HTF_ACT_TANH, r_cut > 0.0f, d_rows != nullptr, l_max == 2, nlist_dtype == HTF_F64);
         const int rl = check_launch("at_sweep_kernel");
         if (rl != HTF_OK) return rl;
     }

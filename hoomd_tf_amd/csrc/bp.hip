@@ -58,16 +58,6 @@ int dtrain_reduce_launch(const float *d_partials, unsigned nparts, unsigned n, f
     return check_launch("dtrain_reduce_kernel");
 }
 
-namespace {
-
-int bp_check(unsigned B, unsigned n_rows, float r_cut) {
-    HTF_REQUIRE(n_rows <= B, "descriptor network: n_rows %u > B %u", n_rows, B);
-    HTF_REQUIRE(r_cut >= 0.0f && r_cut <= 3.402823466e+38f, "descriptor network: r_cut = %g must be finite and positive, or 0 for none",
-                (double)r_cut);
-    return HTF_OK;
-}
-
-} // namespace
 } // namespace htf
 
 extern "C" int htf_bp_forces(const void *d_nlist, int nlist_dtype, unsigned B, unsigned NN, unsigned K, unsigned n_types, unsigned H1,
@@ -77,36 +67,17 @@ extern "C" int htf_bp_forces(const void *d_nlist, int nlist_dtype, unsigned B, u
     int rc = desc_check(d_nlist, nlist_dtype, B, NN, K, n_types, d_mu, gap, d_force, force_dtype);
     if (rc != HTF_OK) return rc;
     if ((rc = desc_check_network(d_weights, H1, H2, activation)) != HTF_OK) return rc;
-    if ((rc = bp_check(B, n_rows, r_cut)) != HTF_OK) return rc;
+    if ((rc = desc_check_rows(B, n_rows, r_cut)) != HTF_OK) return rc;
     if (n_rows == 0) return HTF_OK;
     const size_t lds = desc_lds_forces(K, n_types, H1, H2);
     const int out_f64 = force_dtype == HTF_F64;
     const hipStream_t s = (hipStream_t)stream;
-#define HTF_BK(TANH, VIR, CUT, LIST, T, V4)                                                                                            \
-    hipLaunchKernelGGL((bp_rows_kernel<true, TANH, VIR, CUT, LIST, T>), dim3(desc_grid(n_rows)), dim3(256), lds, s, (const V4 *)d_nlist, \
-                       d_rows, n_rows, NN, d_weights, d_mu, (int)K, (int)n_types, (int)H1, (int)H2, gap, r_cut, d_force, out_f64,        \
-                       d_virial9)
-#define HTF_BK1(TANH, VIR, CUT, LIST)                                                                                                  \
-    do {                                                                                                                               \
-        if (nlist_dtype == HTF_F32) HTF_BK(TANH, VIR, CUT, LIST, float, float4); else HTF_BK(TANH, VIR, CUT, LIST, double, double4);   \
-    } while (0)
-#define HTF_BK2(TANH, VIR, CUT)                                                                                                        \
-    do {                                                                                                                               \
-        if (d_rows) HTF_BK1(TANH, VIR, CUT, true); else HTF_BK1(TANH, VIR, CUT, false);                                                \
-    } while (0)
-#define HTF_BK3(TANH, VIR)                                                                                                             \
-    do {                                                                                                                               \
-        if (r_cut > 0.0f) HTF_BK2(TANH, VIR, true); else HTF_BK2(TANH, VIR, false);                                                    \
-    } while (0)
-    if (activation == HTF_ACT_TANH) {
-        if (d_virial9) HTF_BK3(true, true); else HTF_BK3(true, false);
-    } else {
-        if (d_virial9) HTF_BK3(false, true); else HTF_BK3(false, false);
-    }
-#undef HTF_BK3
-#undef HTF_BK2
-#undef HTF_BK1
-#undef HTF_BK
+    desc_dispatch([&](auto TANH, auto VIR, auto CUT, auto LIST, auto F64) {
+        using IT = desc_in_t<F64>;
+        hipLaunchKernelGGL((bp_rows_kernel<true, TANH, VIR, CUT, LIST, IT>), dim3(desc_grid(n_rows)), dim3(256), lds, s,
+                           (const typename Vec4<IT>::type *)d_nlist, d_rows, n_rows, NN, d_weights, d_mu, (int)K, (int)n_types, (int)H1,
+                           (int)H2, gap, r_cut, d_force, out_f64, d_virial9);
+    }, activation == HTF_ACT_TANH, d_virial9 != nullptr, r_cut > 0.0f, d_rows != nullptr, nlist_dtype == HTF_F64);
     return check_launch("bp_rows_kernel");
 }
 
@@ -115,21 +86,17 @@ extern "C" int htf_bp_descriptor(const void *d_nlist, int nlist_dtype, unsigned 
     using namespace htf;
     int rc = desc_check(d_nlist, nlist_dtype, B, NN, K, n_types, d_mu, gap, d_out, out_dtype);
     if (rc != HTF_OK) return rc;
-    if ((rc = bp_check(B, B, r_cut)) != HTF_OK) return rc;
+    if ((rc = desc_check_rows(B, B, r_cut)) != HTF_OK) return rc;
     if (B == 0) return HTF_OK;
     const size_t lds = desc_lds_descriptor(K);
     const int out_f64 = out_dtype == HTF_F64;
     const hipStream_t s = (hipStream_t)stream;
-#define HTF_BG(CUT, T, V4)                                                                                                        \
-    hipLaunchKernelGGL((bp_rows_kernel<false, false, false, CUT, false, T>), dim3(desc_grid(B)), dim3(256), lds, s, (const V4 *)d_nlist,  \
-                       (const int *)nullptr, B, NN, (const float *)nullptr, d_mu, (int)K, (int)n_types, 0, 0, gap, r_cut, d_out,   \
-                       out_f64, nullptr)
-    if (r_cut > 0.0f) {
-        if (nlist_dtype == HTF_F32) HTF_BG(true, float, float4); else HTF_BG(true, double, double4);
-    } else {
-        if (nlist_dtype == HTF_F32) HTF_BG(false, float, float4); else HTF_BG(false, double, double4);
-    }
-#undef HTF_BG
+    desc_dispatch([&](auto CUT, auto F64) {
+        using IT = desc_in_t<F64>;
+        hipLaunchKernelGGL((bp_rows_kernel<false, false, false, CUT, false, IT>), dim3(desc_grid(B)), dim3(256), lds, s,
+                           (const typename Vec4<IT>::type *)d_nlist, (const int *)nullptr, B, NN, (const float *)nullptr, d_mu, (int)K,
+                           (int)n_types, 0, 0, gap, r_cut, d_out, out_f64, nullptr);
+    }, r_cut > 0.0f, nlist_dtype == HTF_F64);
     return check_launch("bp_rows_kernel");
 }
 
@@ -147,7 +114,7 @@ extern "C" int htf_bp_loss_grad(const void *d_nlist, int nlist_dtype, unsigned B
     int rc = dtrain_check_call(d_nlist, nlist_dtype, B, NN, K, n_types, H1, H2, activation, d_weights, d_mu, gap, d_labels, labels_dtype,
                                d_pred, d_accum, d_scratch);
     if (rc != HTF_OK) return rc;
-    if ((rc = bp_check(B, n_rows, r_cut)) != HTF_OK) return rc;
+    if ((rc = desc_check_rows(B, n_rows, r_cut)) != HTF_OK) return rc;
     if (!d_accum) return HTF_OK;   // (B = 0 and nothing to zero-fill: no launch)
     const unsigned n = 1u + dtrain_params(K * n_types, H1, H2);
     const unsigned grid = dtrain_grid(n_rows);   // (0 for no rows: the reduction alone then writes zeros)
@@ -155,26 +122,12 @@ extern "C" int htf_bp_loss_grad(const void *d_nlist, int nlist_dtype, unsigned B
     if (grid) {
         const size_t lds = dtrain_lds(K, n_types, H1, H2);
         const int l64 = labels_dtype == HTF_F64;
-#define HTF_BT(TANH, CUT, LIST, T, V4)                                                                                                 \
-    hipLaunchKernelGGL((bp_sweep_kernel<TANH, CUT, LIST, T>), dim3(grid), dim3(256), lds, s, (const V4 *)d_nlist, d_rows, n_rows, NN,   \
-                       d_weights, d_mu, (int)K, (int)n_types, (int)H1, (int)H2, gap, r_cut, d_labels, l64, (const float4 *)d_pred,      \
-                       d_scratch)
-#define HTF_BT1(TANH, CUT, LIST)                                                                                                       \
-    do {                                                                                                                               \
-        if (nlist_dtype == HTF_F32) HTF_BT(TANH, CUT, LIST, float, float4); else HTF_BT(TANH, CUT, LIST, double, double4);             \
-    } while (0)
-#define HTF_BT2(TANH, CUT)                                                                                                             \
-    do {                                                                                                                               \
-        if (d_rows) HTF_BT1(TANH, CUT, true); else HTF_BT1(TANH, CUT, false);                                                          \
-    } while (0)
-        if (activation == HTF_ACT_TANH) {
-            if (r_cut > 0.0f) HTF_BT2(true, true); else HTF_BT2(true, false);
-        } else {
-            if (r_cut > 0.0f) HTF_BT2(false, true); else HTF_BT2(false, false);
-        }
-#undef HTF_BT2
-#undef HTF_BT1
-#undef HTF_BT
+        desc_dispatch([&](auto TANH, auto CUT, auto LIST, auto F64) {
+            using IT = desc_in_t<F64>;
+            hipLaunchKernelGGL((bp_sweep_kernel<TANH, CUT, LIST, IT>), dim3(grid), dim3(256), lds, s,
+                               (const typename Vec4<IT>::type *)d_nlist, d_rows, n_rows, NN, d_weights, d_mu, (int)K, (int)n_types,
+                               (int)H1, (int)H2, gap, r_cut, d_labels, l64, (const float4 *)d_pred, d_scratch);
+        }, activation == HTF_ACT_TANH, r_cut > 0.0f, d_rows != nullptr, nlist_dtype == HTF_F64);
         const int rl = check_launch("bp_sweep_kernel");
         if (rl != HTF_OK) return rl;
     }

@@ -182,25 +182,12 @@ extern "C" int htf_cf_grad(const void *d_nlist, int nlist_dtype, unsigned B, uns
     if (n_rows == 0) return HTF_OK;
     const size_t lds = desc_lds_forces(K, n_types, H1, H2);
     const hipStream_t s = (hipStream_t)stream;
-#define HTF_CG(TANH, CUT, LIST, T, V4)                                                                                               \
-    hipLaunchKernelGGL((cf_grad_kernel<TANH, CUT, LIST, T>), dim3(desc_grid(n_rows)), dim3(256), lds, s, (const V4 *)d_nlist, d_rows,  \
-                       n_rows, NN, d_weights, d_mu, (int)K, (int)n_types, (int)H1, (int)H2, gap, r_cut, d_g, d_energy)
-#define HTF_CG1(TANH, CUT, LIST)                                                                                                     \
-    do {                                                                                                                             \
-        if (nlist_dtype == HTF_F32) HTF_CG(TANH, CUT, LIST, float, float4); else HTF_CG(TANH, CUT, LIST, double, double4);           \
-    } while (0)
-#define HTF_CG2(TANH, CUT)                                                                                                           \
-    do {                                                                                                                             \
-        if (d_rows) HTF_CG1(TANH, CUT, true); else HTF_CG1(TANH, CUT, false);                                                        \
-    } while (0)
-    if (activation == HTF_ACT_TANH) {
-        if (r_cut > 0.0f) HTF_CG2(true, true); else HTF_CG2(true, false);
-    } else {
-        if (r_cut > 0.0f) HTF_CG2(false, true); else HTF_CG2(false, false);
-    }
-#undef HTF_CG2
-#undef HTF_CG1
-#undef HTF_CG
+    desc_dispatch([&](auto TANH, auto CUT, auto LIST, auto F64) {
+        using IT = desc_in_t<F64>;
+        hipLaunchKernelGGL((cf_grad_kernel<TANH, CUT, LIST, IT>), dim3(desc_grid(n_rows)), dim3(256), lds, s,
+                           (const typename Vec4<IT>::type *)d_nlist, d_rows, n_rows, NN, d_weights, d_mu, (int)K, (int)n_types, (int)H1,
+                           (int)H2, gap, r_cut, d_g, d_energy);
+    }, activation == HTF_ACT_TANH, r_cut > 0.0f, d_rows != nullptr, nlist_dtype == HTF_F64);
     return check_launch("cf_grad_kernel");
 }
 
@@ -220,25 +207,12 @@ extern "C" int htf_cf_forces_ghost(const void *d_nlist, int nlist_dtype, const i
     const int out_f64 = force_dtype == HTF_F64;
     const bool wide = K % 4u == 0 && ((uintptr_t)d_g & 15u) == 0;
     const hipStream_t s = (hipStream_t)stream;
-#define HTF_CF(VIR, CUT, WIDE, T, V4)                                                                                                \
-    hipLaunchKernelGGL((cf_pair_force_kernel<VIR, CUT, WIDE, T>), dim3(desc_grid(B)), dim3(256), lds, s, (const V4 *)d_nlist, d_index, \
-                       d_types, B, n_table, NN, d_mu, (int)K, (int)n_types, gap, r_cut, d_g, d_energy, d_force, out_f64, d_virial9)
-#define HTF_CF1(VIR, CUT, WIDE)                                                                                                      \
-    do {                                                                                                                             \
-        if (nlist_dtype == HTF_F32) HTF_CF(VIR, CUT, WIDE, float, float4); else HTF_CF(VIR, CUT, WIDE, double, double4);             \
-    } while (0)
-#define HTF_CF2(VIR, CUT)                                                                                                            \
-    do {                                                                                                                             \
-        if (wide) HTF_CF1(VIR, CUT, true); else HTF_CF1(VIR, CUT, false);                                                            \
-    } while (0)
-    if (d_virial9) {
-        if (r_cut > 0.0f) HTF_CF2(true, true); else HTF_CF2(true, false);
-    } else {
-        if (r_cut > 0.0f) HTF_CF2(false, true); else HTF_CF2(false, false);
-    }
-#undef HTF_CF2
-#undef HTF_CF1
-#undef HTF_CF
+    desc_dispatch([&](auto VIR, auto CUT, auto WIDE, auto F64) {
+        using IT = desc_in_t<F64>;
+        hipLaunchKernelGGL((cf_pair_force_kernel<VIR, CUT, WIDE, IT>), dim3(desc_grid(B)), dim3(256), lds, s,
+                           (const typename Vec4<IT>::type *)d_nlist, d_index, d_types, B, n_table, NN, d_mu, (int)K, (int)n_types, gap,
+                           r_cut, d_g, d_energy, d_force, out_f64, d_virial9);
+    }, d_virial9 != nullptr, r_cut > 0.0f, wide, nlist_dtype == HTF_F64);
     return check_launch("cf_pair_force_kernel");
 }
 

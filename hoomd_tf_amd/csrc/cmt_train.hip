@@ -319,29 +319,14 @@ extern "C" int htf_cmt_loss_grad(const void *d_nlist, int nlist_dtype, const int
     const unsigned grid = cmt_train_grid(n_rows, n_models);   // (0 for no rows: the reductions alone then write zeros)
     const hipStream_t s = (hipStream_t)stream;
     if (grid) {
-#define HTF_CMT_T(TANH, CUT, LIST, T, V4)                                                                                            \
-    do {                                                                                                                             \
-        if ((rc = cmt_train_raise_lds(committee_train_kernel<TANH, CUT, LIST, T>, lds)) != HTF_OK) return rc;                         \
-        hipLaunchKernelGGL((committee_train_kernel<TANH, CUT, LIST, T>), dim3(grid), dim3(64 * n_models), lds, s,                     \
-                           (const V4 *)d_nlist, d_index, d_rows, n_rows, B, NN, d_weights, weight_stride, d_mu, (int)K, (int)n_types, \
-                           (int)H1, (int)H2, gap, r_cut, (const float4 *)d_rho, d_scratch);                                          \
-    } while (0)
-#define HTF_CMT_T1(TANH, CUT, LIST)                                                                                                  \
-    do {                                                                                                                             \
-        if (nlist_dtype == HTF_F32) HTF_CMT_T(TANH, CUT, LIST, float, float4); else HTF_CMT_T(TANH, CUT, LIST, double, double4);     \
-    } while (0)
-#define HTF_CMT_T2(TANH, CUT)                                                                                                        \
-    do {                                                                                                                             \
-        if (d_rows) HTF_CMT_T1(TANH, CUT, true); else HTF_CMT_T1(TANH, CUT, false);                                                  \
-    } while (0)
-        if (activation == HTF_ACT_TANH) {
-            if (r_cut > 0.0f) HTF_CMT_T2(true, true); else HTF_CMT_T2(true, false);
-        } else {
-            if (r_cut > 0.0f) HTF_CMT_T2(false, true); else HTF_CMT_T2(false, false);
-        }
-#undef HTF_CMT_T2
-#undef HTF_CMT_T1
-#undef HTF_CMT_T
+        desc_dispatch([&](auto TANH, auto CUT, auto LIST, auto F64) {
+            using IT = desc_in_t<F64>;
+            if ((rc = cmt_train_raise_lds(committee_train_kernel<TANH, CUT, LIST, IT>, lds)) != HTF_OK) return;
+            hipLaunchKernelGGL((committee_train_kernel<TANH, CUT, LIST, IT>), dim3(grid), dim3(64 * n_models), lds, s,
+                               (const typename Vec4<IT>::type *)d_nlist, d_index, d_rows, n_rows, B, NN, d_weights, weight_stride, d_mu,
+                               (int)K, (int)n_types, (int)H1, (int)H2, gap, r_cut, (const float4 *)d_rho, d_scratch);
+        }, activation == HTF_ACT_TANH, r_cut > 0.0f, d_rows != nullptr, nlist_dtype == HTF_F64);
+        if (rc != HTF_OK) return rc;
         const int rl = check_launch("committee_train_kernel");
         if (rl != HTF_OK) return rl;
     }

@@ -44,26 +44,12 @@ extern "C" int htf_ct_loss_grad_ghost(const void *d_nlist, int nlist_dtype, cons
     const hipStream_t s = (hipStream_t)stream;
     if (grid) {
         const size_t lds = dtrain_lds(K, n_types, H1, H2);
-#define HTF_CT(TANH, CUT, LIST, T, V4)                                                                                                 \
-    hipLaunchKernelGGL((ct_sweep_kernel<TANH, CUT, LIST, T>), dim3(grid), dim3(256), lds, s, (const V4 *)d_nlist, d_index, d_rows,      \
-                       n_rows, n_table, NN, d_weights, d_mu, (int)K, (int)n_types, (int)H1, (int)H2, gap, r_cut, (const float4 *)d_rho, \
-                       d_scratch)
-#define HTF_CT1(TANH, CUT, LIST)                                                                                                       \
-    do {                                                                                                                               \
-        if (nlist_dtype == HTF_F32) HTF_CT(TANH, CUT, LIST, float, float4); else HTF_CT(TANH, CUT, LIST, double, double4);             \
-    } while (0)
-#define HTF_CT2(TANH, CUT)                                                                                                             \
-    do {                                                                                                                               \
-        if (d_rows) HTF_CT1(TANH, CUT, true); else HTF_CT1(TANH, CUT, false);                                                          \
-    } while (0)
-        if (activation == HTF_ACT_TANH) {
-            if (r_cut > 0.0f) HTF_CT2(true, true); else HTF_CT2(true, false);
-        } else {
-            if (r_cut > 0.0f) HTF_CT2(false, true); else HTF_CT2(false, false);
-        }
-#undef HTF_CT2
-#undef HTF_CT1
-#undef HTF_CT
+        desc_dispatch([&](auto TANH, auto CUT, auto LIST, auto F64) {
+            using IT = desc_in_t<F64>;
+            hipLaunchKernelGGL((ct_sweep_kernel<TANH, CUT, LIST, IT>), dim3(grid), dim3(256), lds, s,
+                               (const typename Vec4<IT>::type *)d_nlist, d_index, d_rows, n_rows, n_table, NN, d_weights, d_mu, (int)K,
+                               (int)n_types, (int)H1, (int)H2, gap, r_cut, (const float4 *)d_rho, d_scratch);
+        }, activation == HTF_ACT_TANH, r_cut > 0.0f, d_rows != nullptr, nlist_dtype == HTF_F64);
         const int rl = check_launch("ct_sweep_kernel");
         if (rl != HTF_OK) return rl;
     }

@@ -646,22 +646,43 @@ class DescriptorMLP:
             o += c
         return out, rows   # (rows: kept alive by the caller until its launches are queued)
 
+    class _Args:
+        """The argument groups the family's C entries share (include/htf_bp.h and its followers), formed once per call on ``x``
+        (checked here): ``pair`` the pair tensor and its dtype, ``shape`` (B, NN), ``rbf`` (K, n_types, mu, gap) as the entries
+        without a network take them, ``net(d_w)`` (K, n_types, H1, H2, act, w, mu, gap), ``rows(d_rows, n_rows)`` with the
+        cutoff behind them (``r_cut``, 0 for none), and the stream.  A call site composes them in its entry's order."""
+
+        def __init__(self, lay, x):
+            self.B, self.NN = self.shape = lay._check(x)
+            self.pair = (x.data_ptr(), ops._dt(x))
+            self.rbf = (lay.K, lay.n_types, lay.mu.data_ptr(), float(lay.gap))
+            self.widths = (lay.K, lay.n_types, lay.H1, lay.H2, _lib.ACT_TANH if lay.activation == "tanh" else _lib.ACT_LINEAR)
+            self.r_cut = float(lay.r_cut or 0.0)
+            self.stream = ops._stream(x)
+
+        def net(self, d_w):
+            return self.widths + (d_w,) + self.rbf[2:]
+
+        def rows(self, d_rows, n_rows):
+            return (d_rows, n_rows, self.r_cut)
+
+    @staticmethod
+    def _dst(out, v):
+        """Forces, their dtype and the virial (or none) as the force entries take them."""
+        return (out.data_ptr(), ops._dt(out), v.data_ptr() if v is not None else None)
+
     def forces(self, x, virial=False, species=None):
         """The kernel on a pair-vector tensor ``x`` [B, NN, 4] (fp32 or fp64): forces [B, 4] in ``x``'s dtype, and the
         [B, 3, 3] virial when ``virial``.  compute_nlist_forces calls this for the layer's energy.  ``species``: [B] or
         [B, 4] (column 3), needed when ``n_species > 1``."""
         self._no_angular("forces")
         self._no_committee("forces")
-        B, NN = self._check(x)
-        out = torch.empty((B, 4), dtype=x.dtype, device=x.device)
-        v = torch.empty((B, 3, 3), dtype=x.dtype, device=x.device) if virial else None
-        act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
+        a = self._Args(self, x)
+        out = torch.empty((a.B, 4), dtype=x.dtype, device=x.device)
+        v = torch.empty((a.B, 3, 3), dtype=x.dtype, device=x.device) if virial else None
         launches, rows = self._launches(species, x)
         for _, d_rows, n_rows, d_w in launches:   # every row is in exactly one list: no memset
-            check(lib.htf_bp_forces(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, d_w,
-                                    self.mu.data_ptr(), float(self.gap), out.data_ptr(), ops._dt(out),
-                                    v.data_ptr() if v is not None else None, d_rows, n_rows, float(self.r_cut or 0.0),
-                                    ops._stream(x)))
+            check(lib.htf_bp_forces(*a.pair, *a.shape, *a.net(d_w), *self._dst(out, v), *a.rows(d_rows, n_rows), a.stream))
         return (out, v) if virial else out
 
     def _no_angular(self, what):
@@ -721,7 +742,8 @@ class DescriptorMLP:
                                       "one member there" % (self.n_models, n_ghost))
         if members and self.n_models == 1:
             raise ValueError("DescriptorMLP: total_forces(members=True) is a committee's (n_models > 1)")
-        B, NN = self._check(x)
+        a = self._Args(self, x)
+        B, M = a.B, self.n_models
         index = self._slot_index(index, x)
         own = None
         if self.n_types > 1:
@@ -736,64 +758,34 @@ class DescriptorMLP:
             own = (types[:, 3] if types.dim() == 2 else types).detach().to(torch.float32).contiguous()
         out = torch.empty((B, 4), dtype=x.dtype, device=x.device)
         v = torch.empty((B, 3, 3), dtype=x.dtype, device=x.device) if virial else None
-        e = torch.empty((B,), dtype=torch.float32, device=x.device)
-        act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
+
+        def f32(*shape):
+            return torch.empty(shape, dtype=torch.float32, device=x.device)
+
+        # the family: its two entries, the table pass 1 writes and pass 2 gathers from, and what each entry takes of its own
+        dev = mem = None
+        if M > 1:        # include/htf_committee.h: the two sweeps for all members at once
+            grad, forces, table, e = lib.htf_cmt_grad, lib.htf_cmt_forces, f32(B, M, self.D), f32(B, M)
+            dev, mem = f32(B, 2), f32(M, B, 4) if members else None
+            own1, own2 = (M, self.n_species * self.P), (M, dev.data_ptr(), mem.data_ptr() if members else None)
+        elif self.l_max:   # include/htf_angular.h: the table {g, p, S} per row and channel in place of g
+            grad, forces, e = lib.htf_ang_grad, lib.htf_ang_forces_ghost, f32(B)
+            table = f32(B + n_ghost, self.Dr, 4 if self.l_max == 1 else 10)
+            own1, own2 = (self.l_max,), (self.l_max, B + n_ghost)
+        else:            # include/htf_cforce.h; pass 2 by include/htf_cghost.h, whose n_table = B is the plain entry
+            grad, forces, table, e = lib.htf_cf_grad, lib.htf_cf_forces_ghost, f32(B + n_ghost, self.D), f32(B)
+            own1, own2 = (), (B + n_ghost,)
         launches, rows = self._launches(species, x)
-        if self.n_models > 1:   # include/htf_committee.h: the two sweeps for all members at once
-            M = self.n_models
-            g = torch.empty((B, M, self.D), dtype=torch.float32, device=x.device)
-            e = torch.empty((B, M), dtype=torch.float32, device=x.device)
-            dev = torch.empty((B, 2), dtype=torch.float32, device=x.device)
-            mem = torch.empty((M, B, 4), dtype=torch.float32, device=x.device) if members else None
-            for _, d_rows, n_rows, d_w in launches:   # pass 1: every row is in exactly one list
-                check(lib.htf_cmt_grad(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, d_w,
-                                       self.mu.data_ptr(), float(self.gap), g.data_ptr(), e.data_ptr(), d_rows, n_rows,
-                                       float(self.r_cut or 0.0), M, self.n_species * self.P, ops._stream(x)))
-            check(lib.htf_cmt_forces(x.data_ptr(), ops._dt(x), index.data_ptr(), own.data_ptr() if own is not None else None, B,
-                                     NN, self.K, self.n_types, self.mu.data_ptr(), float(self.gap), g.data_ptr(), e.data_ptr(),
-                                     out.data_ptr(), ops._dt(out), v.data_ptr() if v is not None else None,
-                                     float(self.r_cut or 0.0), M, dev.data_ptr(), mem.data_ptr() if members else None,
-                                     ops._stream(x)))
-            self.deviation = dev
-            res = (out, v) if virial else (out,)
-            if members:
-                res = res + (mem,)
-            return res if len(res) > 1 else out
-        if self.l_max:   # include/htf_angular.h: the table {g, p, S} per row and channel in place of g
-            h = torch.empty((B + n_ghost, self.Dr, 4 if self.l_max == 1 else 10), dtype=torch.float32, device=x.device)
-            for _, d_rows, n_rows, d_w in launches:
-                check(lib.htf_ang_grad(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, d_w,
-                                       self.mu.data_ptr(), float(self.gap), h.data_ptr(), e.data_ptr(), d_rows, n_rows,
-                                       float(self.r_cut or 0.0), self.l_max, ops._stream(x)))
-            if n_ghost:
-                halo(h)
-                check(lib.htf_ang_forces_ghost(x.data_ptr(), ops._dt(x), index.data_ptr(), own.data_ptr() if own is not None else None,
-                                               B, NN, self.K, self.n_types, self.mu.data_ptr(), float(self.gap), h.data_ptr(),
-                                               e.data_ptr(), out.data_ptr(), ops._dt(out), v.data_ptr() if v is not None else None,
-                                               float(self.r_cut or 0.0), self.l_max, B + n_ghost, ops._stream(x)))
-                return (out, v) if virial else out
-            check(lib.htf_ang_forces(x.data_ptr(), ops._dt(x), index.data_ptr(), own.data_ptr() if own is not None else None, B,
-                                     NN, self.K, self.n_types, self.mu.data_ptr(), float(self.gap), h.data_ptr(), e.data_ptr(),
-                                     out.data_ptr(), ops._dt(out), v.data_ptr() if v is not None else None,
-                                     float(self.r_cut or 0.0), self.l_max, ops._stream(x)))
-            return (out, v) if virial else out
-        g = torch.empty((B + n_ghost, self.D), dtype=torch.float32, device=x.device)
         for _, d_rows, n_rows, d_w in launches:   # pass 1: every row is in exactly one list
-            check(lib.htf_cf_grad(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, d_w,
-                                  self.mu.data_ptr(), float(self.gap), g.data_ptr(), e.data_ptr(), d_rows, n_rows,
-                                  float(self.r_cut or 0.0), ops._stream(x)))
+            check(grad(*a.pair, *a.shape, *a.net(d_w), table.data_ptr(), e.data_ptr(), *a.rows(d_rows, n_rows), *own1, a.stream))
         if n_ghost:
-            halo(g)
-            check(lib.htf_cf_forces_ghost(x.data_ptr(), ops._dt(x), index.data_ptr(), own.data_ptr() if own is not None else None, B,
-                                          NN, self.K, self.n_types, self.mu.data_ptr(), float(self.gap), g.data_ptr(), e.data_ptr(),
-                                          out.data_ptr(), ops._dt(out), v.data_ptr() if v is not None else None,
-                                          float(self.r_cut or 0.0), B + n_ghost, ops._stream(x)))
-            return (out, v) if virial else out
-        check(lib.htf_cf_forces(x.data_ptr(), ops._dt(x), index.data_ptr(), own.data_ptr() if own is not None else None, B, NN,
-                                self.K, self.n_types, self.mu.data_ptr(), float(self.gap), g.data_ptr(), e.data_ptr(),
-                                out.data_ptr(), ops._dt(out), v.data_ptr() if v is not None else None,
-                                float(self.r_cut or 0.0), ops._stream(x)))
-        return (out, v) if virial else out
+            halo(table)
+        check(forces(*a.pair, index.data_ptr(), own.data_ptr() if own is not None else None, *a.shape, *a.rbf, table.data_ptr(),
+                     e.data_ptr(), *self._dst(out, v), a.r_cut, *own2, a.stream))
+        if M > 1:
+            self.deviation = dev
+        res = (out,) + ((v,) if virial else ()) + ((mem,) if members else ())
+        return res if len(res) > 1 else out
 
     def loss_gradient(self, x, labels, pred=None, accum=None, species=None):
         """One force-matching sweep (htf_bp_loss_grad) over a pair-vector tensor ``x`` [B, NN, 4] (fp32 or fp64) and
@@ -805,24 +797,23 @@ class DescriptorMLP:
         ``s``'s rows, zeros when it has none; each row steps its own slice of ``w``."""
         self._no_angular("loss_gradient")
         self._no_committee("loss_gradient")
-        B, NN = self._check(x)
+        a = self._Args(self, x)
         pred, accum, launches, rows, scratch = self._sweep_buffers(x, labels, pred, accum, species,
                                                                    lambda: self.forces(x, species=species))
-        P = self.P
-        act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
         for s, d_rows, n_rows, d_w in launches:
-            check(lib.htf_bp_loss_grad(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.H1, self.H2, act, d_w,
-                                       self.mu.data_ptr(), float(self.gap), labels.data_ptr(), ops._dt(labels), pred.data_ptr(),
-                                       accum.data_ptr() + 4 * s * (1 + P), scratch.data_ptr(), d_rows, n_rows,
-                                       float(self.r_cut or 0.0), ops._stream(x)))
+            check(lib.htf_bp_loss_grad(*a.pair, *a.shape, *a.net(d_w), labels.data_ptr(), ops._dt(labels), pred.data_ptr(),
+                                       accum.data_ptr() + 4 * s * (1 + self.P), scratch.data_ptr(), *a.rows(d_rows, n_rows),
+                                       a.stream))
         return accum
 
-    def _sweep_buffers(self, x, labels, pred, accum, species, evaluate):
+    def _sweep_buffers(self, x, labels, pred, accum, species, evaluate, members=0, scratch_floats=None):
         """What the force-matching sweeps share ahead of their C calls: the checks of ``labels``, of ``pred`` (``evaluate()``,
         in fp32, when not given) and of ``accum`` (made here when not given), the launches, one scratch buffer, and zeros in the
-        rows of ``accum`` whose species is absent.  Returns (pred, accum, launches, rows, scratch); ``rows`` is what
-        ``_launches`` asks its caller to keep."""
+        rows of ``accum`` whose species is absent.  ``members=M``: the committee's sweep, whose ``pred`` and ``accum`` carry a
+        leading axis of length M; ``scratch_floats(n_rows)``: the floats its entry wants for a launch (htf_bp_scratch_floats
+        when not given).  Returns (pred, accum, launches, rows, scratch); ``rows`` is what ``_launches`` asks its caller to keep."""
         B = int(x.shape[0])
+        lead = (members,) if members else ()
         ops._dev(labels, "labels")
         ops._dt(labels)
         if tuple(labels.shape) != (B, 4) or labels.device != x.device:
@@ -832,25 +823,37 @@ class DescriptorMLP:
             if pred.dtype != torch.float32:
                 pred = pred.to(torch.float32)
         ops._dev(pred, "pred", torch.float32)
-        if tuple(pred.shape) != (B, 4) or pred.device != x.device:
-            raise ValueError("DescriptorMLP: pred must be [%d, 4] on %s, got %s on %s" % (B, x.device, tuple(pred.shape), pred.device))
+        if tuple(pred.shape) != lead + (B, 4) or pred.device != x.device:
+            raise ValueError("DescriptorMLP: pred must be %s on %s%s, got %s on %s" % (
+                list(lead + (B, 4)), x.device, " (total_forces(..., members=True))" if members else "", tuple(pred.shape), pred.device))
         S, P = self.n_species, self.P
+        total = (members or 1) * S * (1 + P)
         if accum is None:
-            accum = torch.empty((S, 1 + P) if S > 1 else (1 + P,), dtype=torch.float32, device=x.device)
+            accum = torch.empty(lead + ((S, 1 + P) if S > 1 else (1 + P,)), dtype=torch.float32, device=x.device)
         ops._dev(accum, "accum", torch.float32)
-        if accum.numel() != S * (1 + P) or accum.device != x.device:
-            raise ValueError("DescriptorMLP: accum must hold %d floats on %s" % (S * (1 + P), x.device))
+        if accum.numel() != total or accum.device != x.device or (members and not accum.is_contiguous()):
+            raise ValueError("DescriptorMLP: accum must hold %d %sfloats on %s" % (total, "contiguous " if members else "", x.device))
         launches, rows = self._launches(species, x)
         # one scratch buffer for the largest species: the launches run one after the other on the stream
-        # (sized for D = K n_types (1 + l_max) inputs: P is this layer's)
-        scratch = torch.empty(max(1, int(lib.htf_bp_scratch_floats(max([n for _, _, n, _ in launches] or [0]), self.K,
-                                                                   self.n_types * (1 + self.l_max), self.H1, self.H2))),
-                              dtype=torch.float32, device=x.device)
+        # (htf_bp_scratch_floats sized for D = K n_types (1 + l_max) inputs: P is this layer's)
+        n_max = max([n for _, _, n, _ in launches] or [0])
+        floats = (scratch_floats(n_max) if scratch_floats else
+                  lib.htf_bp_scratch_floats(n_max, self.K, self.n_types * (1 + self.l_max), self.H1, self.H2))
+        scratch = torch.empty(max(1, int(floats)), dtype=torch.float32, device=x.device)
         present = {s for s, _, _, _ in launches}   # (every other row of accum is written by its species' launch)
         for s in range(S):
             if s not in present:
-                accum.view(S, 1 + P)[s].zero_()
+                accum.view(-1, S, 1 + P)[:, s].zero_()
         return pred, accum, launches, rows, scratch
+
+    def _sweep(self, entry, a, index, rho, buffers, own):
+        """The launches of a sweep on the forces of the total energy: ``entry`` once per species present, on the residual table
+        ``rho``, with what ``_sweep_buffers`` returned; ``own``: what the entry takes of its own ahead of the stream."""
+        _, accum, launches, _, scratch = buffers
+        for s, d_rows, n_rows, d_w in launches:   # (d_w: species s, of member 0 in a committee; its row of accum likewise)
+            check(entry(*a.pair, index.data_ptr(), *a.shape, *a.net(d_w), rho.data_ptr(), accum.data_ptr() + 4 * s * (1 + self.P),
+                        scratch.data_ptr(), *a.rows(d_rows, n_rows), *own, a.stream))
+        return accum
 
     def total_loss_gradient(self, x, labels, index, types=None, pred=None, accum=None, species=None, n_ghost=0, halo=None):
         """One force-matching sweep on the forces of the total energy (htf_ct_loss_grad, include/htf_ctrain.h): ``accum`` as
@@ -890,42 +893,19 @@ class DescriptorMLP:
         """The sweep on the forces of the total energy for this layer's ``l_max``: htf_ct_loss_grad, or htf_at_loss_grad; with
         ghost rows their twins of include/htf_cghost.h on the residual table of ``B + n_ghost`` rows."""
         n_ghost = self._ghost_rows(n_ghost, halo, what)
-        B, NN = self._check(x)
+        a = self._Args(self, x)
         index = self._slot_index(index, x)
-        pred, accum, launches, rows, scratch = self._sweep_buffers(
+        buffers = self._sweep_buffers(
             x, labels, pred, accum, species,
             lambda: self.total_forces(x, index, types=types, species=species, n_ghost=n_ghost, halo=halo))
-        P = self.P
-        act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
+        n_table = a.B + n_ghost
+        rho = torch.empty((n_table, 4), dtype=torch.float32, device=x.device)
+        torch.sub(buffers[0].detach(), labels.detach().to(torch.float32), out=rho[:a.B])
         if n_ghost:
-            rho = torch.empty((B + n_ghost, 4), dtype=torch.float32, device=x.device)
-            torch.sub(pred.detach(), labels.detach().to(torch.float32), out=rho[:B])
             halo(rho)
-            for s, d_rows, n_rows, d_w in launches:
-                if self.l_max:
-                    check(lib.htf_at_loss_grad_ghost(x.data_ptr(), ops._dt(x), index.data_ptr(), B, NN, self.K, self.n_types, self.H1,
-                                                     self.H2, act, d_w, self.mu.data_ptr(), float(self.gap), rho.data_ptr(),
-                                                     accum.data_ptr() + 4 * s * (1 + P), scratch.data_ptr(), d_rows, n_rows,
-                                                     float(self.r_cut or 0.0), self.l_max, B + n_ghost, ops._stream(x)))
-                else:
-                    check(lib.htf_ct_loss_grad_ghost(x.data_ptr(), ops._dt(x), index.data_ptr(), B, NN, self.K, self.n_types, self.H1,
-                                                     self.H2, act, d_w, self.mu.data_ptr(), float(self.gap), rho.data_ptr(),
-                                                     accum.data_ptr() + 4 * s * (1 + P), scratch.data_ptr(), d_rows, n_rows,
-                                                     float(self.r_cut or 0.0), B + n_ghost, ops._stream(x)))
-            return accum
-        rho = (pred.detach() - labels.detach().to(torch.float32)).contiguous()
-        for s, d_rows, n_rows, d_w in launches:
-            if self.l_max:
-                check(lib.htf_at_loss_grad(x.data_ptr(), ops._dt(x), index.data_ptr(), B, NN, self.K, self.n_types, self.H1, self.H2,
-                                           act, d_w, self.mu.data_ptr(), float(self.gap), rho.data_ptr(),
-                                           accum.data_ptr() + 4 * s * (1 + P), scratch.data_ptr(), d_rows, n_rows,
-                                           float(self.r_cut or 0.0), self.l_max, ops._stream(x)))
-                continue
-            check(lib.htf_ct_loss_grad(x.data_ptr(), ops._dt(x), index.data_ptr(), B, NN, self.K, self.n_types, self.H1, self.H2,
-                                       act, d_w, self.mu.data_ptr(), float(self.gap), rho.data_ptr(),
-                                       accum.data_ptr() + 4 * s * (1 + P), scratch.data_ptr(), d_rows, n_rows,
-                                       float(self.r_cut or 0.0), ops._stream(x)))
-        return accum
+        if self.l_max:
+            return self._sweep(lib.htf_at_loss_grad_ghost, a, index, rho, buffers, (self.l_max, n_table))
+        return self._sweep(lib.htf_ct_loss_grad_ghost, a, index, rho, buffers, (n_table,))
 
     def committee_loss_gradient(self, x, labels, index, types=None, pred=None, accum=None, species=None):
         """``total_loss_gradient`` for every member of a committee in one sweep (htf_cmt_loss_grad, include/htf_cmt_train.h):
@@ -941,57 +921,25 @@ class DescriptorMLP:
         if self.n_models < 2:
             raise ValueError("DescriptorMLP: committee_loss_gradient() is a committee's (n_models > 1); "
                              "total_loss_gradient(x, labels, index) is the sweep of this single network")
-        B, NN = self._check(x)
+        a = self._Args(self, x)
         index = self._slot_index(index, x)
         M, S, P = self.n_models, self.n_species, self.P
-        ops._dev(labels, "labels")
-        ops._dt(labels)
-        if tuple(labels.shape) != (B, 4) or labels.device != x.device:
-            raise ValueError("DescriptorMLP: labels must be [%d, 4] on %s, got %s on %s" % (B, x.device, tuple(labels.shape), labels.device))
-        if pred is None:
-            pred = self.total_forces(x, index, types=types, species=species, members=True)[-1]
-        ops._dev(pred, "pred", torch.float32)
-        if tuple(pred.shape) != (M, B, 4) or pred.device != x.device:
-            raise ValueError("DescriptorMLP: pred must be [%d, %d, 4] on %s (total_forces(..., members=True)), got %s on %s"
-                             % (M, B, x.device, tuple(pred.shape), pred.device))
-        if accum is None:
-            accum = torch.empty((M, S, 1 + P) if S > 1 else (M, 1 + P), dtype=torch.float32, device=x.device)
-        ops._dev(accum, "accum", torch.float32)
-        if accum.numel() != M * S * (1 + P) or accum.device != x.device or not accum.is_contiguous():
-            raise ValueError("DescriptorMLP: accum must hold %d contiguous floats on %s" % (M * S * (1 + P), x.device))
-        launches, rows = self._launches(species, x)
-        # one scratch buffer for the largest species: the launches run one after the other on the stream
-        scratch = torch.empty(max(1, int(lib.htf_cmt_scratch_floats(max([n for _, _, n, _ in launches] or [0]), self.K,
-                                                                    self.n_types, self.H1, self.H2, M))),
-                              dtype=torch.float32, device=x.device)
-        present = {s for s, _, _, _ in launches}   # (every other row of accum is written by its species' launch)
-        for s in range(S):
-            if s not in present:
-                accum.view(M, S, 1 + P)[:, s].zero_()
+        buffers = self._sweep_buffers(
+            x, labels, pred, accum, species, lambda: self.total_forces(x, index, types=types, species=species, members=True)[-1],
+            members=M, scratch_floats=lambda n: lib.htf_cmt_scratch_floats(n, self.K, self.n_types, self.H1, self.H2, M))
         # [B][M][4]: a particle's residuals are one record of 16 M bytes
-        rho = (pred.detach() - labels.detach().to(torch.float32).unsqueeze(0)).permute(1, 0, 2).contiguous()
-        act = _lib.ACT_TANH if self.activation == "tanh" else _lib.ACT_LINEAR
-        for s, d_rows, n_rows, d_w in launches:   # (d_w: species s of member 0; members S P floats apart)
-            check(lib.htf_cmt_loss_grad(x.data_ptr(), ops._dt(x), index.data_ptr(), B, NN, self.K, self.n_types, self.H1, self.H2,
-                                        act, d_w, self.mu.data_ptr(), float(self.gap), rho.data_ptr(),
-                                        accum.data_ptr() + 4 * s * (1 + P), scratch.data_ptr(), d_rows, n_rows,
-                                        float(self.r_cut or 0.0), M, S * P, S * (1 + P), ops._stream(x)))
-        return accum
+        rho = (buffers[0].detach() - labels.detach().to(torch.float32).unsqueeze(0)).permute(1, 0, 2).contiguous()
+        return self._sweep(lib.htf_cmt_loss_grad, a, index, rho, buffers, (M, S * P, S * (1 + P)))   # (members S P floats apart)
 
     def descriptor(self, nlist):
         """The network input [B, D] alone (the kernel's first stage), in the dtype of the pair-vector tensor: G, or
         [G | A | Q] with ``l_max > 0``."""
         self._no_committee("descriptor")
         x = simmodel._as_nlist(nlist).tensor
-        B, NN = self._check(x)
-        out = torch.empty((B, self.D), dtype=x.dtype, device=x.device)
-        if self.l_max:
-            check(lib.htf_ang_descriptor(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.mu.data_ptr(), float(self.gap),
-                                         out.data_ptr(), ops._dt(out), float(self.r_cut or 0.0), self.l_max, ops._stream(x)))
-            simmodel._trace_log().append({"op": "descriptor"})
-            return out
-        check(lib.htf_bp_descriptor(x.data_ptr(), ops._dt(x), B, NN, self.K, self.n_types, self.mu.data_ptr(), float(self.gap),
-                                    out.data_ptr(), ops._dt(out), float(self.r_cut or 0.0), ops._stream(x)))
+        a = self._Args(self, x)
+        out = torch.empty((a.B, self.D), dtype=x.dtype, device=x.device)
+        entry, own = (lib.htf_ang_descriptor, (self.l_max,)) if self.l_max else (lib.htf_bp_descriptor, ())
+        check(entry(*a.pair, *a.shape, *a.rbf, out.data_ptr(), ops._dt(out), a.r_cut, *own, a.stream))
         simmodel._trace_log().append({"op": "descriptor"})   # (no replay: a model calling it keeps the eager path)
         return out
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Resource class of the descriptor family's kernels (bp_*, dtrain*, cf_*, ct_*, ang_*, at_*) in two builds of libhtf_amd.so,
+"""Resource class of the descriptor family's kernels (bp_*, dtrain*, cf_*, ct_*, ang_*, at_*, cmt_*, committee_*) in two builds of libhtf_amd.so,
 read from the code-object notes (no GPU): VGPRs, the waves per SIMD they allow, SGPRs, scratch, VGPR and SGPR spills and
 static LDS.  Prints one markdown row per kernel whose figures differ (--all: every kernel) and a summary; exits 1 if a kernel
 of the second library has scratch or VGPR spills, spills more SGPRs (to VGPR lanes) than in the first, allows fewer waves per
@@ -17,7 +17,7 @@ import sys
 import tempfile
 
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-FAMILY = re.compile(r"^htf::(bp_|dtrain|cf_|ct_|ang_|at_)")
+FAMILY = re.compile(r"^htf::(bp_|dtrain|cf_|ct_|ang_|at_|cmt_|committee_)")
 KEYS = ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count", "group_segment_fixed_size")
 
 

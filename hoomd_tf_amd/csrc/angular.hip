@@ -428,8 +428,8 @@ extern "C" int htf_ang_grad(const void *d_nlist, int nlist_dtype, unsigned B, un
     if (n_rows == 0) return HTF_OK;
     const size_t lds = desc_lds_forces(K, n_types * (1 + l_max), H1, H2);   // (the weights of D = K n_types (1 + l_max) inputs)
     const hipStream_t s = (hipStream_t)stream;
-    desc_dispatch([&](auto TANH, auto CUT, auto L2, auto F64) {
-        using IT = desc_in_t<F64>;
+    dispatch_flags([&](auto TANH, auto CUT, auto L2, auto F64) {
+        using IT = scalar_t<F64>;
         hipLaunchKernelGGL((ang_grad_kernel<TANH, CUT, L2 ? 2 : 1, IT>), dim3(desc_grid(n_rows)), dim3(256), lds, s,
                            (const typename Vec4<IT>::type *)d_nlist, d_rows, n_rows, NN, d_weights, d_mu, (int)K, (int)n_types, (int)H1,
                            (int)H2, gap, r_cut, d_table, d_energy);
@@ -453,8 +453,8 @@ extern "C" int htf_ang_forces_ghost(const void *d_nlist, int nlist_dtype, const 
     const size_t lds = ang_lds_forces(K);
     const int out_f64 = force_dtype == HTF_F64;
     const hipStream_t s = (hipStream_t)stream;
-    desc_dispatch([&](auto VIR, auto CUT, auto L2, auto F64) {
-        using IT = desc_in_t<F64>;
+    dispatch_flags([&](auto VIR, auto CUT, auto L2, auto F64) {
+        using IT = scalar_t<F64>;
         hipLaunchKernelGGL((ang_force_kernel<VIR, CUT, L2 ? 2 : 1, IT>), dim3(desc_grid(B)), dim3(256), lds, s,
                            (const typename Vec4<IT>::type *)d_nlist, d_index, d_types, B, n_table, NN, d_mu, (int)K, (int)n_types, gap,
                            r_cut, d_table, d_energy, d_force, out_f64, d_virial9);
@@ -481,8 +481,8 @@ extern "C" int htf_ang_descriptor(const void *d_nlist, int nlist_dtype, unsigned
     const size_t lds = desc_lds_descriptor(K);
     const int out_f64 = out_dtype == HTF_F64;
     const hipStream_t s = (hipStream_t)stream;
-    desc_dispatch([&](auto CUT, auto L2, auto F64) {
-        using IT = desc_in_t<F64>;
+    dispatch_flags([&](auto CUT, auto L2, auto F64) {
+        using IT = scalar_t<F64>;
         hipLaunchKernelGGL((ang_desc_kernel<CUT, L2 ? 2 : 1, IT>), dim3(desc_grid(B)), dim3(256), lds, s,
                            (const typename Vec4<IT>::type *)d_nlist, B, NN, d_mu, (int)K, (int)n_types, gap, r_cut, d_out, out_f64);
     }, r_cut > 0.0f, l_max == 2, nlist_dtype == HTF_F64);

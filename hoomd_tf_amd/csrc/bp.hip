@@ -72,8 +72,8 @@ extern "C" int htf_bp_forces(const void *d_nlist, int nlist_dtype, unsigned B, u
     const size_t lds = desc_lds_forces(K, n_types, H1, H2);
     const int out_f64 = force_dtype == HTF_F64;
     const hipStream_t s = (hipStream_t)stream;
-    desc_dispatch([&](auto TANH, auto VIR, auto CUT, auto LIST, auto F64) {
-        using IT = desc_in_t<F64>;
+    dispatch_flags([&](auto TANH, auto VIR, auto CUT, auto LIST, auto F64) {
+        using IT = scalar_t<F64>;
         hipLaunchKernelGGL((bp_rows_kernel<true, TANH, VIR, CUT, LIST, IT>), dim3(desc_grid(n_rows)), dim3(256), lds, s,
                            (const typename Vec4<IT>::type *)d_nlist, d_rows, n_rows, NN, d_weights, d_mu, (int)K, (int)n_types, (int)H1,
                            (int)H2, gap, r_cut, d_force, out_f64, d_virial9);
@@ -91,8 +91,8 @@ extern "C" int htf_bp_descriptor(const void *d_nlist, int nlist_dtype, unsigned 
     const size_t lds = desc_lds_descriptor(K);
     const int out_f64 = out_dtype == HTF_F64;
     const hipStream_t s = (hipStream_t)stream;
-    desc_dispatch([&](auto CUT, auto F64) {
-        using IT = desc_in_t<F64>;
+    dispatch_flags([&](auto CUT, auto F64) {
+        using IT = scalar_t<F64>;
         hipLaunchKernelGGL((bp_rows_kernel<false, false, false, CUT, false, IT>), dim3(desc_grid(B)), dim3(256), lds, s,
                            (const typename Vec4<IT>::type *)d_nlist, (const int *)nullptr, B, NN, (const float *)nullptr, d_mu, (int)K,
                            (int)n_types, 0, 0, gap, r_cut, d_out, out_f64, nullptr);
@@ -122,8 +122,8 @@ extern "C" int htf_bp_loss_grad(const void *d_nlist, int nlist_dtype, unsigned B
     if (grid) {
         const size_t lds = dtrain_lds(K, n_types, H1, H2);
         const int l64 = labels_dtype == HTF_F64;
-        desc_dispatch([&](auto TANH, auto CUT, auto LIST, auto F64) {
-            using IT = desc_in_t<F64>;
+        dispatch_flags([&](auto TANH, auto CUT, auto LIST, auto F64) {
+            using IT = scalar_t<F64>;
             hipLaunchKernelGGL((bp_sweep_kernel<TANH, CUT, LIST, IT>), dim3(grid), dim3(256), lds, s,
                                (const typename Vec4<IT>::type *)d_nlist, d_rows, n_rows, NN, d_weights, d_mu, (int)K, (int)n_types,
                                (int)H1, (int)H2, gap, r_cut, d_labels, l64, (const float4 *)d_pred, d_scratch);

@@ -182,8 +182,8 @@ extern "C" int htf_cf_grad(const void *d_nlist, int nlist_dtype, unsigned B, uns
     if (n_rows == 0) return HTF_OK;
     const size_t lds = desc_lds_forces(K, n_types, H1, H2);
     const hipStream_t s = (hipStream_t)stream;
-    desc_dispatch([&](auto TANH, auto CUT, auto LIST, auto F64) {
-        using IT = desc_in_t<F64>;
+    dispatch_flags([&](auto TANH, auto CUT, auto LIST, auto F64) {
+        using IT = scalar_t<F64>;
         hipLaunchKernelGGL((cf_grad_kernel<TANH, CUT, LIST, IT>), dim3(desc_grid(n_rows)), dim3(256), lds, s,
                            (const typename Vec4<IT>::type *)d_nlist, d_rows, n_rows, NN, d_weights, d_mu, (int)K, (int)n_types, (int)H1,
                            (int)H2, gap, r_cut, d_g, d_energy);
@@ -207,8 +207,8 @@ extern "C" int htf_cf_forces_ghost(const void *d_nlist, int nlist_dtype, const i
     const int out_f64 = force_dtype == HTF_F64;
     const bool wide = K % 4u == 0 && ((uintptr_t)d_g & 15u) == 0;
     const hipStream_t s = (hipStream_t)stream;
-    desc_dispatch([&](auto VIR, auto CUT, auto WIDE, auto F64) {
-        using IT = desc_in_t<F64>;
+    dispatch_flags([&](auto VIR, auto CUT, auto WIDE, auto F64) {
+        using IT = scalar_t<F64>;
         hipLaunchKernelGGL((cf_pair_force_kernel<VIR, CUT, WIDE, IT>), dim3(desc_grid(B)), dim3(256), lds, s,
                            (const typename Vec4<IT>::type *)d_nlist, d_index, d_types, B, n_table, NN, d_mu, (int)K, (int)n_types, gap,
                            r_cut, d_g, d_energy, d_force, out_f64, d_virial9);

@@ -319,8 +319,8 @@ extern "C" int htf_cmt_loss_grad(const void *d_nlist, int nlist_dtype, const int
     const unsigned grid = cmt_train_grid(n_rows, n_models);   // (0 for no rows: the reductions alone then write zeros)
     const hipStream_t s = (hipStream_t)stream;
     if (grid) {
-        desc_dispatch([&](auto TANH, auto CUT, auto LIST, auto F64) {
-            using IT = desc_in_t<F64>;
+        dispatch_flags([&](auto TANH, auto CUT, auto LIST, auto F64) {
+            using IT = scalar_t<F64>;
             if ((rc = cmt_train_raise_lds(committee_train_kernel<TANH, CUT, LIST, IT>, lds)) != HTF_OK) return;
             hipLaunchKernelGGL((committee_train_kernel<TANH, CUT, LIST, IT>), dim3(grid), dim3(64 * n_models), lds, s,
                                (const typename Vec4<IT>::type *)d_nlist, d_index, d_rows, n_rows, B, NN, d_weights, weight_stride, d_mu,

@@ -436,8 +436,8 @@ extern "C" int htf_cmt_grad(const void *d_nlist, int nlist_dtype, unsigned B, un
                 n_models, lds, HTF_CMT_MAX_LDS_BYTES);
     if (n_rows == 0) return HTF_OK;
     const hipStream_t s = (hipStream_t)stream;
-    desc_dispatch([&](auto TANH, auto CUT, auto LIST, auto F64) {
-        using IT = desc_in_t<F64>;
+    dispatch_flags([&](auto TANH, auto CUT, auto LIST, auto F64) {
+        using IT = scalar_t<F64>;
         if ((rc = cmt_raise_lds(cmt_grad_kernel<TANH, CUT, LIST, IT>, lds)) != HTF_OK) return;
         hipLaunchKernelGGL((cmt_grad_kernel<TANH, CUT, LIST, IT>), dim3(cmt_grid_grad(n_rows)), dim3(kCmtGradThreads), lds, s,
                            (const typename Vec4<IT>::type *)d_nlist, d_rows, n_rows, NN, d_weights, weight_stride, (int)n_models, d_mu,
@@ -463,8 +463,8 @@ extern "C" int htf_cmt_forces(const void *d_nlist, int nlist_dtype, const int *d
     const int out_f64 = force_dtype == HTF_F64;
     const bool wide = K % 4u == 0 && ((uintptr_t)d_g & 15u) == 0;
     const hipStream_t s = (hipStream_t)stream;
-    desc_dispatch([&](auto VIR, auto CUT, auto WIDE, auto F64) {
-        using IT = desc_in_t<F64>;
+    dispatch_flags([&](auto VIR, auto CUT, auto WIDE, auto F64) {
+        using IT = scalar_t<F64>;
         hipLaunchKernelGGL((cmt_force_kernel<VIR, CUT, WIDE, IT>), dim3(desc_grid(B)), dim3(256), lds, s,
                            (const typename Vec4<IT>::type *)d_nlist, d_index, d_types, B, NN, d_mu, (int)K, (int)n_types, (int)n_models,
                            gap, r_cut, d_g, d_energy, d_force, out_f64, d_virial9, d_dev, d_members);

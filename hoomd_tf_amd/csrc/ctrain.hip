@@ -44,8 +44,8 @@ extern "C" int htf_ct_loss_grad_ghost(const void *d_nlist, int nlist_dtype, cons
     const hipStream_t s = (hipStream_t)stream;
     if (grid) {
         const size_t lds = dtrain_lds(K, n_types, H1, H2);
-        desc_dispatch([&](auto TANH, auto CUT, auto LIST, auto F64) {
-            using IT = desc_in_t<F64>;
+        dispatch_flags([&](auto TANH, auto CUT, auto LIST, auto F64) {
+            using IT = scalar_t<F64>;
             hipLaunchKernelGGL((ct_sweep_kernel<TANH, CUT, LIST, IT>), dim3(grid), dim3(256), lds, s,
                                (const typename Vec4<IT>::type *)d_nlist, d_index, d_rows, n_rows, n_table, NN, d_weights, d_mu, (int)K,
                                (int)n_types, (int)H1, (int)H2, gap, r_cut, (const float4 *)d_rho, d_scratch);

@@ -26,7 +26,7 @@
 //         Outputs are indexed by the row.  Without it the row index costs the default route nothing.
 #ifndef HTF_DESC_ROW_H_
 #define HTF_DESC_ROW_H_
-#include <type_traits>
+#include "dispatch.h"
 #include "htf_common.h"
 #include "htf_internal.h"
 #include "pair_math.h"
@@ -350,16 +350,6 @@ inline unsigned desc_grid(unsigned n) {
     const unsigned g = (n + 3u) / 4u;
     return g < kDescMaxBlocks ? g : kDescMaxBlocks;
 }
-
-// Run-time flags to compile-time constants: f is called once with one std::true_type / std::false_type per flag, in the order
-// given, so a launch site names its kernel and its arguments once whatever the number of template switches.  Only the flag
-// combinations the call can take are instantiated; a switch an entry fixes stays a literal in its lambda.
-template <typename F> inline void desc_dispatch(F &&f) { f(); }
-template <typename F, typename... Bs> inline void desc_dispatch(F &&f, bool b, Bs... rest) {
-    if (b) desc_dispatch([&](auto... t) { f(std::true_type{}, t...); }, rest...);
-    else   desc_dispatch([&](auto... t) { f(std::false_type{}, t...); }, rest...);
-}
-template <bool F64> using desc_in_t = std::conditional_t<F64, double, float>;   // the pair tensor's scalar
 
 } // namespace
 } // namespace htf

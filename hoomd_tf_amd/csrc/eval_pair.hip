@@ -161,15 +161,9 @@ __global__ __launch_bounds__(256) void eval_pair_kernel(const typename Vec4<IT>:
 #ifdef HTF_JIT_UNIT
 } // namespace htf  (a generated unit takes the templates above and nothing else of this file)
 #else
-template <int KIND, int G, bool VIRIAL, typename IT>
-static int launch_eval_g(const void *nlist, unsigned B, unsigned NN, void *force, void *virial9,
-                         int out_f64, const PotParams &p, const unsigned *counts, hipStream_t stream) {
-    constexpr unsigned rows_per_block = 4 * (64 / G);
-    unsigned grid = (B + rows_per_block - 1) / rows_per_block;
-    hipLaunchKernelGGL((eval_pair_kernel<KIND, G, VIRIAL, IT>), dim3(grid), dim3(256), 0, stream,
-                       (const typename Vec4<IT>::type *)nlist, B, NN, force, virial9, out_f64, p, counts);
-    return check_launch("eval_pair_kernel");
-}
+} // namespace htf
+#include "dispatch.h" // (host side only)
+namespace htf {
 
 // lanes per particle row: 8 slots per lane where NN allows (NN=128 -> 16 lanes)
 static int pick_group(unsigned NN) {
@@ -178,42 +172,27 @@ static int pick_group(unsigned NN) {
     return 4;
 }
 
-template <int KIND, bool VIRIAL, typename IT>
-static int launch_eval_k(const void *nlist, unsigned B, unsigned NN, void *force, void *virial9,
-                         int out_f64, const PotParams &p, const unsigned *counts, hipStream_t stream) {
-    switch (pick_group(NN)) {
-    case 16: return launch_eval_g<KIND, 16, VIRIAL, IT>(nlist, B, NN, force, virial9, out_f64, p, counts, stream);
-    case 8: return launch_eval_g<KIND, 8, VIRIAL, IT>(nlist, B, NN, force, virial9, out_f64, p, counts, stream);
-    default: return launch_eval_g<KIND, 4, VIRIAL, IT>(nlist, B, NN, force, virial9, out_f64, p, counts, stream);
-    }
-}
-
-template <int KIND>
-static int launch_eval(const void *nlist, int in_dtype, unsigned B, unsigned NN, void *force,
-                       void *virial9, int out_f64, const PotParams &p, const unsigned *counts, hipStream_t stream) {
-    if (in_dtype == HTF_F32) {
-        return virial9 ? launch_eval_k<KIND, true, float>(nlist, B, NN, force, virial9, out_f64, p, counts, stream)
-                       : launch_eval_k<KIND, false, float>(nlist, B, NN, force, virial9, out_f64, p, counts, stream);
-    }
-    return virial9 ? launch_eval_k<KIND, true, double>(nlist, B, NN, force, virial9, out_f64, p, counts, stream)
-                   : launch_eval_k<KIND, false, double>(nlist, B, NN, force, virial9, out_f64, p, counts, stream);
-}
-
 int eval_pair_dispatch(const PotParams &p, const void *nlist, int in_dtype, unsigned B, unsigned NN,
                        void *force, int force_dtype, void *virial9, const unsigned *counts, hipStream_t stream) {
     const int out_f64 = force_dtype == HTF_F64;
-    switch (p.kind) {
-    case HTF_POT_LJ: return launch_eval<HTF_POT_LJ>(nlist, in_dtype, B, NN, force, virial9, out_f64, p, counts, stream);
-    case HTF_POT_WCA: return launch_eval<HTF_POT_WCA>(nlist, in_dtype, B, NN, force, virial9, out_f64, p, counts, stream);
-    case HTF_POT_RINV_POLY: return launch_eval<HTF_POT_RINV_POLY>(nlist, in_dtype, B, NN, force, virial9, out_f64, p, counts, stream);
-    case HTF_POT_SIMPLE: return launch_eval<HTF_POT_SIMPLE>(nlist, in_dtype, B, NN, force, virial9, out_f64, p, counts, stream);
-    case HTF_POT_GAUSS: return launch_eval<HTF_POT_GAUSS>(nlist, in_dtype, B, NN, force, virial9, out_f64, p, counts, stream);
-    case HTF_POT_LJ_PARAM: return launch_eval<HTF_POT_LJ_PARAM>(nlist, in_dtype, B, NN, force, virial9, out_f64, p, counts, stream);
-    case HTF_POT_JIT: return jit_launch_eval(p, nlist, in_dtype, B, NN, force, virial9, out_f64, counts, stream);
-    default:
+    if (p.kind == HTF_POT_JIT) return jit_launch_eval(p, nlist, in_dtype, B, NN, force, virial9, out_f64, counts, stream);
+    const int group = pick_group(NN);
+    const unsigned rows_per_block = 4 * (64 / group);
+    const unsigned grid = (B + rows_per_block - 1) / rows_per_block;
+    const bool closed = dispatch_value<HTF_POT_LJ, HTF_POT_WCA, HTF_POT_RINV_POLY, HTF_POT_SIMPLE, HTF_POT_GAUSS, HTF_POT_LJ_PARAM>([&](auto KIND) {
+        dispatch_value<4, 8, 16>([&](auto G) {
+            dispatch_flags([&](auto VIRIAL, auto F64) {
+                using IT = scalar_t<F64>;
+                hipLaunchKernelGGL((eval_pair_kernel<KIND, G, VIRIAL, IT>), dim3(grid), dim3(256), 0, stream,
+                                   (const typename Vec4<IT>::type *)nlist, B, NN, force, virial9, out_f64, p, counts);
+            }, virial9 != nullptr, in_dtype != HTF_F32);
+        }, group);
+    }, p.kind);
+    if (!closed) {
         set_error("eval_pair_dispatch: potential kind %d is not a closed-form pair potential", p.kind);
         return HTF_ERR_INVALID;
     }
+    return check_launch("eval_pair_kernel");
 }
 
 // ---- two potentials in one pass (EDS-biased models: base potential + Gaussian CV channel) ----
@@ -311,41 +290,19 @@ __global__ __launch_bounds__(256) void eval_pair2_kernel(const typename Vec4<IT>
     }
 }
 
-template <int KA, int G, typename IT>
-static int launch_eval2_g(const void *nlist, unsigned B, unsigned NN, void *fa, void *fb, int out_f64,
-                          const PotParams &pa, const PotParams &pb, float *partials, const RdfArgs &rdf, hipStream_t stream) {
-    constexpr unsigned rows_per_block = 4 * (64 / G);
-    unsigned grid = (B + rows_per_block - 1) / rows_per_block;
-    if (grid > 2048u) grid = 2048u; // persistent: 8 blocks per CU
-    hipLaunchKernelGGL((eval_pair2_kernel<KA, G, IT>), dim3(grid), dim3(256), 0, stream,
-                       (const typename Vec4<IT>::type *)nlist, B, NN, fa, fb, out_f64, pa, pb, partials, rdf);
-    return check_launch("eval_pair2_kernel");
-}
-
-template <int KA, typename IT>
-static int launch_eval2_k(const void *nlist, unsigned B, unsigned NN, void *fa, void *fb, int out_f64,
-                          const PotParams &pa, const PotParams &pb, float *partials, const RdfArgs &rdf,
-                          hipStream_t stream) {
-    // 16 lanes per row at every NN: this two-kernel form is the fallback of the one-kernel sweep (fused_eval.hip), which is what
-    // config C4 runs; the 8- and 4-lane groups for short rows exist in variants builds only
+// 16 lanes per row at every NN: this two-kernel form is the fallback of the one-kernel sweep (fused_eval.hip), which is what
+// config C4 runs; the 8- and 4-lane groups for short rows exist in variants builds only
+static int pick_group2(unsigned NN) {
 #ifdef HTF_AB_VARIANTS
-    switch (pick_group(NN)) {
-    case 16: return launch_eval2_g<KA, 16, IT>(nlist, B, NN, fa, fb, out_f64, pa, pb, partials, rdf, stream);
-    case 8: return launch_eval2_g<KA, 8, IT>(nlist, B, NN, fa, fb, out_f64, pa, pb, partials, rdf, stream);
-    default: return launch_eval2_g<KA, 4, IT>(nlist, B, NN, fa, fb, out_f64, pa, pb, partials, rdf, stream);
-    }
+    return pick_group(NN);
 #else
-    return launch_eval2_g<KA, 16, IT>(nlist, B, NN, fa, fb, out_f64, pa, pb, partials, rdf, stream);
+    (void)NN;
+    return 16;
 #endif
 }
 
 unsigned eval_pair2_num_partials(unsigned B, unsigned NN) {
-#ifdef HTF_AB_VARIANTS
-    const unsigned rows_per_block = 4 * (64 / pick_group(NN));
-#else
-    (void)NN;
-    const unsigned rows_per_block = 4 * (64 / 16);
-#endif
+    const unsigned rows_per_block = 4 * (64 / pick_group2(NN));
     return (B + rows_per_block - 1) / rows_per_block;
 }
 
@@ -358,17 +315,26 @@ int eval_pair2_dispatch(const PotParams &pa, const PotParams &pb, const void *nl
         set_error("htf_eval_forces2: bad fused rdf arguments (nbins+2 = %u, range [%g, %g])", rdf_nbins_total, rdf_r0, rdf_r1);
         return HTF_ERR_INVALID;
     }
-#define HTF_E2(K) (in_dtype == HTF_F32 ? launch_eval2_k<K, float>(nlist, B, NN, forceA, forceB, out_f64, pa, pb, partials, rdf, stream) \
-                                       : launch_eval2_k<K, double>(nlist, B, NN, forceA, forceB, out_f64, pa, pb, partials, rdf, stream))
-    switch (pa.kind) {
-    case HTF_POT_LJ: return HTF_E2(HTF_POT_LJ);
-    case HTF_POT_WCA: return HTF_E2(HTF_POT_WCA);
-    case HTF_POT_RINV_POLY: return HTF_E2(HTF_POT_RINV_POLY);
-    default:
+    unsigned grid = eval_pair2_num_partials(B, NN);
+    if (grid > 2048u) grid = 2048u; // persistent: 8 blocks per CU
+    const bool closed = dispatch_value<HTF_POT_LJ, HTF_POT_WCA, HTF_POT_RINV_POLY>([&](auto KA) {
+#ifdef HTF_AB_VARIANTS
+        dispatch_value<4, 8, 16>([&](auto G) {
+#else
+        dispatch_value<16>([&](auto G) {
+#endif
+            dispatch_flags([&](auto F64) {
+                using IT = scalar_t<F64>;
+                hipLaunchKernelGGL((eval_pair2_kernel<KA, G, IT>), dim3(grid), dim3(256), 0, stream,
+                                   (const typename Vec4<IT>::type *)nlist, B, NN, forceA, forceB, out_f64, pa, pb, partials, rdf);
+            }, in_dtype != HTF_F32);
+        }, pick_group2(NN));
+    }, pa.kind);
+    if (!closed) {
         set_error("htf_eval_forces2: base potential kind %d is not a closed-form rinv potential", pa.kind);
         return HTF_ERR_INVALID;
     }
-#undef HTF_E2
+    return check_launch("eval_pair2_kernel");
 }
 
 __global__ __launch_bounds__(1024) void reduce_partials_kernel(const float *__restrict__ partials, unsigned n, float scale,
@@ -449,10 +415,10 @@ extern "C" int htf_nlist_rinv(const void *d_nlist, int nlist_dtype, unsigned B, 
     size_t n = (size_t)B * NN;
     if (n == 0) return HTF_OK;
     unsigned grid = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    if (nlist_dtype == HTF_F32)
-        hipLaunchKernelGGL((nlist_rinv_kernel<float>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float4 *)d_nlist, n, d_out);
-    else
-        hipLaunchKernelGGL((nlist_rinv_kernel<double>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const double4 *)d_nlist, n, d_out);
+    dispatch_flags([&](auto F64) {
+        using IT = scalar_t<F64>;
+        hipLaunchKernelGGL((nlist_rinv_kernel<IT>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const typename Vec4<IT>::type *)d_nlist, n, d_out);
+    }, nlist_dtype != HTF_F32);
     return check_launch("nlist_rinv_kernel");
 }
 
@@ -465,10 +431,10 @@ extern "C" int htf_check_nlist(const void *d_nlist, int nlist_dtype, unsigned B,
     constexpr int G = 16;
     constexpr unsigned rows_per_block = 4 * (64 / G);
     unsigned grid = (B + rows_per_block - 1) / rows_per_block;
-    if (nlist_dtype == HTF_F32)
-        hipLaunchKernelGGL((check_nlist_kernel<float, G>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float4 *)d_nlist, B, NN, d_out);
-    else
-        hipLaunchKernelGGL((check_nlist_kernel<double, G>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const double4 *)d_nlist, B, NN, d_out);
+    dispatch_flags([&](auto F64) {
+        using IT = scalar_t<F64>;
+        hipLaunchKernelGGL((check_nlist_kernel<IT, G>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const typename Vec4<IT>::type *)d_nlist, B, NN, d_out);
+    }, nlist_dtype != HTF_F32);
     return check_launch("check_nlist_kernel");
 }
 

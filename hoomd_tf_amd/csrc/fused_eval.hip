@@ -747,6 +747,16 @@ __global__ __launch_bounds__(256) void fused_forces_rows2_kernel(
 #ifdef HTF_JIT_UNIT
 } // namespace htf  (a generated unit takes the templates above and nothing else of this file)
 #else
+} // namespace htf
+#include "dispatch.h" // (host side only)
+namespace htf {
+// the merged-tail or the plain rows kernel of a launch: the two take the same arguments
+template <bool TAILS, int KIND, bool STORE, int R, typename PT, int EP>
+constexpr auto fused_rows_kernel() {
+    if constexpr (TAILS) return &fused_forces_tails_kernel<KIND, STORE, R, PT, EP>;
+    else return &fused_forces_rows2_kernel<KIND, STORE, R, PT, EP>;
+}
+
 template <int KIND, bool VIRIAL, typename PT>
 static int launch_fused(const void *pos, unsigned N, unsigned NN, unsigned offset, unsigned batch, const htf_box *hb,
                         const unsigned *n_neigh, const unsigned *nlist, const unsigned *head_list, double rmax,
@@ -777,22 +787,20 @@ static int launch_fused(const void *pos, unsigned N, unsigned NN, unsigned offse
         constexpr const char *tails_env = nullptr;
 #endif
         static const int n_cu = device_cu_count();
-#define HTF_ROWS_LAUNCH_EP(ST, RR, EPV, EPP)                                                                           \
-    HTF_LAUNCH_TIMED((fused_forces_rows2_kernel<KIND, ST, RR, PT, kEpilogueKind ? EPV : 0>), dim3(grid), dim3(256), s,  \
-                     (const typename Vec4<PT>::type *)pos, N, NN, offset, batch, b, n_neigh, nlist, head_list,         \
-                     (PT)(rc * rc), force, out_f64, p, check_count, positions_out, dest, counts_io, EPP)
-#define HTF_ROWS_LAUNCH(ST, RR)                                                                                        \
-    const unsigned full = ((batch + RR - 1) / RR + 3) / 4;                                                             \
-    const unsigned grid = per_cu > 0 && (unsigned)(per_cu * n_cu) < full ? (unsigned)(per_cu * n_cu) : full;           \
-    do {                                                                                                               \
-        if (kEpilogueKind && ep != nullptr && ep_level >= 2) {                                                         \
-            HTF_ROWS_LAUNCH_EP(ST, RR, 2, ep);                                                                         \
-        } else if (kEpilogueKind && ep != nullptr) {                                                                   \
-            HTF_ROWS_LAUNCH_EP(ST, RR, 1, ep);                                                                         \
-        } else {                                                                                                       \
-            HTF_ROWS_LAUNCH_EP(ST, RR, 0, (const StepEpilogue<PT> *)nullptr);                                          \
-        }                                                                                                              \
-    } while (0)
+        // R rows per wave, merged tails or plain: the epilogue level and the tensor store picked once, for either kernel
+        const int ep_form = kEpilogueKind && ep != nullptr ? (ep_level >= 2 ? 2 : 1) : 0;
+        const auto launch_rows = [&](auto TAILS, auto R) {
+            const unsigned full = fused_rows_grid(batch, R);
+            const unsigned grid = !TAILS && per_cu > 0 && (unsigned)(per_cu * n_cu) < full ? (unsigned)(per_cu * n_cu) : full;
+            dispatch_value<0, 1, 2>([&](auto EPV) {
+                dispatch_flags([&](auto ST) {
+                    HTF_LAUNCH_TIMED((fused_rows_kernel<TAILS, KIND, ST, R, PT, kEpilogueKind ? EPV : 0>()), dim3(grid), dim3(256), s,
+                                     (const typename Vec4<PT>::type *)pos, N, NN, offset, batch, b, n_neigh, nlist, head_list,
+                                     (PT)(rc * rc), force, out_f64, p, check_count, positions_out, dest, counts_io,
+                                     EPV != 0 ? ep : (const StepEpilogue<PT> *)nullptr);
+                }, dest != nullptr);
+            }, ep_form);
+        };
         // default for fp32 positions and batches of >= 16 384 rows (65 536 until the VALU diet of round 2: at 32 000 rows the
         // four-row form now takes 17.8 us against 19.0-19.4): four rows per wave with their tails in one trip
         // (58.0 us against 60.5 for the two-row form at C3 in isolation, 61.5-62.1 against 62.5-63.3 inside the MD loop,
@@ -813,8 +821,8 @@ static int launch_fused(const void *pos, unsigned N, unsigned NN, unsigned offse
         // potentials BASELINE's configurations time (LJModel, WCARepulsion); the polynomial, the trainable LJ, the Gaussian and
         // SimplePotential take the two-row form at every size (~4 % slower at 131 072 rows).  Three rows per wave, four plain rows,
         // persistent grids and the one-row kernel lost their A/Bs and are compiled in variants builds only.
-        constexpr bool kTails = KIND == HTF_POT_LJ || KIND == HTF_POT_WCA;
-        int tails = batch >= 16384u ? (batch >= 49152u ? 4 : 2) : 0;
+        [[maybe_unused]] constexpr bool kTails = KIND == HTF_POT_LJ || KIND == HTF_POT_WCA; // (variants builds: every kind)
+        int tails = fused_tails_rows(batch);
         // (until the epilogue became ONE copy at the end of a row group the four-row form with a halo-packing epilogue needed 82
         //  VGPRs -- five waves per SIMD -- and lost to the two-row form, 71.5 us against 60.4 at C3; now 58: -DHTF_HALO_FOUR_ROWS=0
         //  restores the old rule for A/B runs)
@@ -827,82 +835,31 @@ static int launch_fused(const void *pos, unsigned N, unsigned NN, unsigned offse
         if (!kTails) tails = 0;
 #endif
         if (tails == 2 || tails == 3 || tails == 4) {
-#define HTF_TAILS_LAUNCH_EP(ST, RR, EPV, EPP)                                                                          \
-    HTF_LAUNCH_TIMED((fused_forces_tails_kernel<KIND, ST, RR, PT, kEpilogueKind ? EPV : 0>), grid_t, dim3(256), s,      \
-                     (const typename Vec4<PT>::type *)pos, N, NN, offset, batch, b, n_neigh, nlist, head_list,         \
-                     (PT)(rc * rc), force, out_f64, p, check_count, positions_out, dest, counts_io, EPP)
-#define HTF_TAILS_LAUNCH(ST, RR)                                                                                       \
-    do {                                                                                                               \
-        const dim3 grid_t(((batch + RR - 1) / RR + 3) / 4);                                                            \
-        if (kEpilogueKind && ep != nullptr && ep_level >= 2) {                                                         \
-            HTF_TAILS_LAUNCH_EP(ST, RR, 2, ep);                                                                        \
-        } else if (kEpilogueKind && ep != nullptr) {                                                                   \
-            HTF_TAILS_LAUNCH_EP(ST, RR, 1, ep);                                                                        \
-        } else {                                                                                                       \
-            HTF_TAILS_LAUNCH_EP(ST, RR, 0, (const StepEpilogue<PT> *)nullptr);                                         \
-        }                                                                                                              \
-    } while (0)
+            const auto launch_tails = [&](auto R) { launch_rows(std::true_type{}, R); };
 #ifdef HTF_AB_VARIANTS
-            if (dest != nullptr) {
-                if (tails == 2) HTF_TAILS_LAUNCH(true, 2); else if (tails == 3) HTF_TAILS_LAUNCH(true, 3); else HTF_TAILS_LAUNCH(true, 4);
-            } else {
-                if (tails == 2) HTF_TAILS_LAUNCH(false, 2); else if (tails == 3) HTF_TAILS_LAUNCH(false, 3); else HTF_TAILS_LAUNCH(false, 4);
-            }
+            dispatch_value<2, 3, 4>(launch_tails, tails);
 #else
-            if constexpr (kTails) {
-                if (dest != nullptr) {
-                    if (tails == 2) HTF_TAILS_LAUNCH(true, 2); else HTF_TAILS_LAUNCH(true, 4);
-                } else {
-                    if (tails == 2) HTF_TAILS_LAUNCH(false, 2); else HTF_TAILS_LAUNCH(false, 4);
-                }
-            }
+            if constexpr (kTails) dispatch_value<2, 4>(launch_tails, tails);
 #endif
-#undef HTF_TAILS_LAUNCH
-#undef HTF_TAILS_LAUNCH_EP
             return check_launch("fused_forces_tails_kernel");
         }
+        const auto launch_plain = [&](auto R) { launch_rows(std::false_type{}, R); };
 #ifdef HTF_AB_VARIANTS
-        if (rows == 2 || rows == 4) {
-            if (rows == 2) {
-                if (dest != nullptr) { HTF_ROWS_LAUNCH(true, 2); } else { HTF_ROWS_LAUNCH(false, 2); }
-            } else {
-                if (dest != nullptr) { HTF_ROWS_LAUNCH(true, 4); } else { HTF_ROWS_LAUNCH(false, 4); }
-            }
-            return check_launch("fused_forces_rows2_kernel");
-        }
+        if (dispatch_value<2, 4>(launch_plain, rows)) return check_launch("fused_forces_rows2_kernel");
 #else
-        if (dest != nullptr) { HTF_ROWS_LAUNCH(true, 2); } else { HTF_ROWS_LAUNCH(false, 2); }
+        dispatch_value<2>(launch_plain, rows);
         return check_launch("fused_forces_rows2_kernel");
 #endif
-#undef HTF_ROWS_LAUNCH
-#undef HTF_ROWS_LAUNCH_EP
     }
 #ifndef HTF_AB_VARIANTS
     if constexpr (VIRIAL) // (the one-row kernel: every virial request; without a virial only in variants builds, HTF_FUSED_ROWS=1)
 #endif
-    {
-        if (dest != nullptr)
-            HTF_LAUNCH_TIMED((fused_forces_kernel<KIND, VIRIAL, true, PT>), dim3((batch + 3) / 4), dim3(256), s,
-                               (const typename Vec4<PT>::type *)pos, N, NN, offset, batch, b, n_neigh, nlist, head_list,
-                               (PT)(rc * rc), force, virial9, out_f64, p, check_count, positions_out, dest, counts_io);
-        else
-            HTF_LAUNCH_TIMED((fused_forces_kernel<KIND, VIRIAL, false, PT>), dim3((batch + 3) / 4), dim3(256), s,
-                               (const typename Vec4<PT>::type *)pos, N, NN, offset, batch, b, n_neigh, nlist, head_list,
-                               (PT)(rc * rc), force, virial9, out_f64, p, check_count, positions_out, dest, counts_io);
-    }
+        dispatch_flags([&](auto ST) {
+            HTF_LAUNCH_TIMED((fused_forces_kernel<KIND, VIRIAL, ST, PT>), dim3(fused_row1_grid(batch)), dim3(256), s,
+                             (const typename Vec4<PT>::type *)pos, N, NN, offset, batch, b, n_neigh, nlist, head_list,
+                             (PT)(rc * rc), force, virial9, out_f64, p, check_count, positions_out, dest, counts_io);
+        }, dest != nullptr);
     return check_launch("fused_forces_kernel");
-}
-
-template <int KIND>
-static int launch_fused_k(const void *pos, int pos_dtype, unsigned N, unsigned NN, unsigned offset, unsigned batch,
-                          const htf_box *hb, const unsigned *n_neigh, const unsigned *nlist,
-                          const unsigned *head_list, double rmax, void *force, void *virial9, int out_f64,
-                          const PotParams &p, unsigned *check_count, float4 *positions_out, float4 *dest,
-                          unsigned *counts_io, hipStream_t s) {
-#define HTF_FUSED(V, T) launch_fused<KIND, V, T>(pos, N, NN, offset, batch, hb, n_neigh, nlist, head_list, rmax, force, virial9, out_f64, p, check_count, positions_out, dest, counts_io, s)
-    if (pos_dtype == HTF_F32) return virial9 ? HTF_FUSED(true, float) : HTF_FUSED(false, float);
-    return virial9 ? HTF_FUSED(true, double) : HTF_FUSED(false, double);
-#undef HTF_FUSED
 }
 
 // ---------------------------------------------------------------------------- config C4 in ONE kernel
@@ -1679,52 +1636,31 @@ static int launch_fused2(const PotParams &pa, const PotParams &pb, const void *p
     // Shipped forms: two rows per wave with merged tails (fp32 positions and the base potentials that vanish far out), the
     // compacting persistent kernel for everything else.  Variants builds: HTF_FUSED2_ROWS = 4 | 2 | 0, HTF_FUSED2_COMPACT = 0
     // (evaluate the candidates in place).
+    const auto launch = [&](auto kernel) { // (both kernels take the same arguments)
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, (const typename Vec4<PT>::type *)pos, N, NN, offset, batch, b, n_neigh,
+                           nlist, head_list, (PT)(rc * rc), fa, fb, out_f64, pa, pb, partials, rdf, dest, counts_io);
+    };
+    if constexpr (KA == HTF_POT_LJ || KA == HTF_POT_WCA || KA == HTF_POT_LJ_PARAM) {
+        const auto launch_tails = [&](auto R) {
+            dispatch_flags([&](auto ST) { launch(&fused_forces2_tails_kernel<KA, ST, R, PT>); }, dest != nullptr);
+        };
+#ifdef HTF_AB_VARIANTS
+        static const char *renv = getenv("HTF_FUSED2_ROWS");
+        const bool tails = dispatch_value<2, 4>(launch_tails, renv ? atoi(renv) : HTF_FUSED2_ROWS_DEFAULT);
+#else
+        constexpr int rows = HTF_FUSED2_ROWS_DEFAULT;
+        const bool tails = (rows == 2 || rows == 4) && dispatch_value<rows>(launch_tails, rows);
+#endif
+        if (tails) return check_launch("fused_forces2_tails_kernel");
+    }
+    // (rows longer than the compaction buffer: NN <= 128 is what the compacting form holds; beyond it the in-place form)
 #ifdef HTF_AB_VARIANTS
     static const char *cenv = getenv("HTF_FUSED2_COMPACT");
     const bool compact = NN <= 128 && (cenv ? atoi(cenv) != 0 : true);
-    static const char *renv = getenv("HTF_FUSED2_ROWS");
-    const int rows = renv ? atoi(renv) : HTF_FUSED2_ROWS_DEFAULT;
 #else
-    constexpr int rows = HTF_FUSED2_ROWS_DEFAULT;
+    const bool compact = NN <= 128;
 #endif
-    if constexpr (KA == HTF_POT_LJ || KA == HTF_POT_WCA || KA == HTF_POT_LJ_PARAM) {
-        if (rows == 2 || rows == 4) {
-#define HTF_F2T_LAUNCH(ST, RR)                                                                                         \
-    hipLaunchKernelGGL((fused_forces2_tails_kernel<KA, ST, RR, PT>), dim3(grid), dim3(256), 0, s,                      \
-                       (const typename Vec4<PT>::type *)pos, N, NN, offset, batch, b, n_neigh, nlist, head_list,       \
-                       (PT)(rc * rc), fa, fb, out_f64, pa, pb, partials, rdf, dest, counts_io)
-#ifdef HTF_AB_VARIANTS
-            if (dest != nullptr) {
-                if (rows == 2) HTF_F2T_LAUNCH(true, 2); else HTF_F2T_LAUNCH(true, 4);
-            } else {
-                if (rows == 2) HTF_F2T_LAUNCH(false, 2); else HTF_F2T_LAUNCH(false, 4);
-            }
-#else
-            if (dest != nullptr) HTF_F2T_LAUNCH(true, HTF_FUSED2_ROWS_DEFAULT); else HTF_F2T_LAUNCH(false, HTF_FUSED2_ROWS_DEFAULT);
-#endif
-#undef HTF_F2T_LAUNCH
-            return check_launch("fused_forces2_tails_kernel");
-        }
-    }
-#define HTF_F2_LAUNCH(ST, CP)                                                                                          \
-    hipLaunchKernelGGL((fused_forces2_kernel<KA, ST, CP, PT>), dim3(grid), dim3(256), 0, s,                            \
-                       (const typename Vec4<PT>::type *)pos, N, NN, offset, batch, b, n_neigh, nlist, head_list,       \
-                       (PT)(rc * rc), fa, fb, out_f64, pa, pb, partials, rdf, dest, counts_io)
-#ifdef HTF_AB_VARIANTS
-    if (dest != nullptr) {
-        if (compact) HTF_F2_LAUNCH(true, true); else HTF_F2_LAUNCH(true, false);
-    } else {
-        if (compact) HTF_F2_LAUNCH(false, true); else HTF_F2_LAUNCH(false, false);
-    }
-#else
-    // (rows longer than the compaction buffer: NN <= 128 is what the compacting form holds; beyond it the in-place form)
-    if (NN <= 128) {
-        if (dest != nullptr) HTF_F2_LAUNCH(true, true); else HTF_F2_LAUNCH(false, true);
-    } else {
-        if (dest != nullptr) HTF_F2_LAUNCH(true, false); else HTF_F2_LAUNCH(false, false);
-    }
-#endif
-#undef HTF_F2_LAUNCH
+    dispatch_flags([&](auto ST, auto CP) { launch(&fused_forces2_kernel<KA, ST, CP, PT>); }, dest != nullptr, compact);
     return check_launch("fused_forces2_kernel");
 }
 
@@ -1748,19 +1684,18 @@ int fused_forces2_impl(const PotParams &pa, const PotParams &pb, const void *pos
     }
     const Rdf2 rdf{rdf_r0, rdf_r1, rdf_nb, rdf_hist, edges};
     const int out_f64 = force_dtype == HTF_F64;
-#define HTF_F2(K)                                                                                                      \
-    (pos_dtype == HTF_F32 ? launch_fused2<K, float>(pa, pb, pos, N, NN, offset, batch, box, n_neigh, nlist, head_list, rmax, fa, fb, out_f64, partials, rdf, dest, counts_io, s) \
-                          : launch_fused2<K, double>(pa, pb, pos, N, NN, offset, batch, box, n_neigh, nlist, head_list, rmax, fa, fb, out_f64, partials, rdf, dest, counts_io, s))
-    switch (pa.kind) {
-    case HTF_POT_LJ: return HTF_F2(HTF_POT_LJ);
-    case HTF_POT_WCA: return HTF_F2(HTF_POT_WCA);
-    case HTF_POT_RINV_POLY: return HTF_F2(HTF_POT_RINV_POLY);
-    case HTF_POT_LJ_PARAM: return HTF_F2(HTF_POT_LJ_PARAM);
-    default:
+    int rc = HTF_OK;
+    const bool closed = dispatch_value<HTF_POT_LJ, HTF_POT_WCA, HTF_POT_RINV_POLY, HTF_POT_LJ_PARAM>([&](auto KA) {
+        dispatch_flags([&](auto F64) {
+            rc = launch_fused2<KA, scalar_t<F64>>(pa, pb, pos, N, NN, offset, batch, box, n_neigh, nlist, head_list, rmax, fa, fb, out_f64,
+                                                  partials, rdf, dest, counts_io, s);
+        }, pos_dtype != HTF_F32);
+    }, pa.kind);
+    if (!closed) {
         set_error("htf_build_eval_forces2: potential kind %d is not a closed-form base potential", pa.kind);
         return HTF_ERR_INVALID;
     }
-#undef HTF_F2
+    return rc;
 }
 
 int fused_forces_impl(const PotParams &p, const void *pos, int pos_dtype, unsigned N, unsigned NN, unsigned offset,
@@ -1773,24 +1708,22 @@ int fused_forces_impl(const PotParams &p, const void *pos, int pos_dtype, unsign
     HTF_REQUIRE(pos_dtype == HTF_F32 || pos_dtype == HTF_F64, "htf_fused_forces: bad position dtype %d", pos_dtype);
     if (batch == 0) return HTF_OK;
     const int out_f64 = force_dtype == HTF_F64;
-#define HTF_FK(K) launch_fused_k<K>(pos, pos_dtype, N, NN, offset, batch, box, n_neigh, nlist, head_list, rmax, force, virial9, out_f64, p, check_count, positions_out, dest, counts_io, s)
-    switch (p.kind) {
-    case HTF_POT_LJ: return HTF_FK(HTF_POT_LJ);
-    case HTF_POT_WCA: return HTF_FK(HTF_POT_WCA);
-    case HTF_POT_RINV_POLY: return HTF_FK(HTF_POT_RINV_POLY);
-    case HTF_POT_GAUSS: return HTF_FK(HTF_POT_GAUSS);
-    case HTF_POT_LJ_PARAM: return HTF_FK(HTF_POT_LJ_PARAM);
-    case HTF_POT_SIMPLE:
-        HTF_REQUIRE(virial9 == nullptr, "htf_fused_forces: SimplePotential has no virial");
-        return HTF_FK(HTF_POT_SIMPLE);
-    case HTF_POT_JIT: // a generated unit's instantiations of the kernels above (csrc/jit.hip)
+    if (p.kind == HTF_POT_JIT) // a generated unit's instantiations of the kernels above (csrc/jit.hip)
         return jit_launch_fused(p, pos, pos_dtype, N, NN, offset, batch, box, n_neigh, nlist, head_list, rmax, force, virial9, out_f64,
                                 check_count, positions_out, dest, counts_io, s);
-    default:
+    if (p.kind == HTF_POT_SIMPLE) HTF_REQUIRE(virial9 == nullptr, "htf_fused_forces: SimplePotential has no virial");
+    int rc = HTF_OK;
+    const bool closed = dispatch_value<HTF_POT_LJ, HTF_POT_WCA, HTF_POT_RINV_POLY, HTF_POT_GAUSS, HTF_POT_LJ_PARAM, HTF_POT_SIMPLE>([&](auto KIND) {
+        dispatch_flags([&](auto VIRIAL, auto F64) {
+            rc = launch_fused<KIND, VIRIAL, scalar_t<F64>>(pos, N, NN, offset, batch, box, n_neigh, nlist, head_list, rmax, force, virial9,
+                                                           out_f64, p, check_count, positions_out, dest, counts_io, s);
+        }, virial9 != nullptr, pos_dtype != HTF_F32);
+    }, p.kind);
+    if (!closed) {
         set_error("htf_fused_forces: potential kind %d has no fused form (the pair-MLP is MFMA-bound, not traffic-bound)", p.kind);
         return HTF_ERR_INVALID;
     }
-#undef HTF_FK
+    return rc;
 }
 
 } // namespace htf

@@ -192,6 +192,14 @@ struct LaunchEvents {
 };
 LaunchEvents &launch_events();
 
+// The form of a fused-step launch without a virial, for the closed forms (fused_eval.hip launch_fused, where the measurements
+// behind the two thresholds are recorded) and for a generated unit's kernels (jit.hip launch_fused_t) alike: rows per wave with
+// their tails merged into one trip, or 0 for the plain two-row form.  Each entry narrows it to the forms it has.
+inline int fused_tails_rows(unsigned batch) { return batch >= 16384u ? (batch >= 49152u ? 4 : 2) : 0; }
+// workgroups of four waves: a wave per group of R rows, or (the one-row kernel of a virial request) per row
+inline unsigned fused_rows_grid(unsigned batch, unsigned R) { return ((batch + R - 1) / R + 3) / 4; }
+inline unsigned fused_row1_grid(unsigned batch) { return (batch + 3) / 4; }
+
 int fused_forces_impl(const PotParams &p, const void *pos, int pos_dtype, unsigned N, unsigned NN, unsigned offset,
                       unsigned batch, const htf_box *box, const unsigned *n_neigh, const unsigned *nlist,
                       const unsigned *head_list, double rmax, void *force, int force_dtype, void *virial9,

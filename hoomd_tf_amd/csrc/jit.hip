@@ -133,17 +133,16 @@ static int launch_fused_t(const PotParams &p, const void *pos, unsigned N, unsig
         void *args[] = {&pos, &N, &NN, &offset, &batch, &b, &n_neigh, &nlist, &head_list, &rc2, &force, &out_f64, &pp, &check_count,
                         &positions_out, &dest, &counts_io};
         static const char *tails_env = getenv("HTF_JIT_TAILS"); // "0": the two-row form at every size (A/B; forces then do not depend on how a step is cut)
-        if (!f64 && batch >= 49152u && !(tails_env && tails_env[0] == '0')) {
-            // launch_fused's rule for the closed forms BASELINE times: four rows per wave, their tails in one trip
-            HTF_CHECK_HIP(hipModuleLaunchKernel(p.jit->tails4[store], ((batch + 3) / 4 + 3) / 4, 1, 1, 256, 1, 1, 0, s, args, nullptr));
+        // launch_fused's rule (htf_internal.h), of which a generated unit carries the four-row merged-tail form for fp32 positions
+        if (!f64 && fused_tails_rows(batch) == 4 && !(tails_env && tails_env[0] == '0')) {
+            HTF_CHECK_HIP(hipModuleLaunchKernel(p.jit->tails4[store], fused_rows_grid(batch, 4), 1, 1, 256, 1, 1, 0, s, args, nullptr));
             return HTF_OK;
         }
-        const unsigned grid = ((batch + 1) / 2 + 3) / 4; // two rows per wave, four waves per workgroup (launch_fused's HTF_ROWS_LAUNCH)
-        HTF_CHECK_HIP(hipModuleLaunchKernel(p.jit->rows2[f64][store], grid, 1, 1, 256, 1, 1, 0, s, args, nullptr));
+        HTF_CHECK_HIP(hipModuleLaunchKernel(p.jit->rows2[f64][store], fused_rows_grid(batch, 2), 1, 1, 256, 1, 1, 0, s, args, nullptr));
     } else {
         void *args[] = {&pos, &N, &NN, &offset, &batch, &b, &n_neigh, &nlist, &head_list, &rc2, &force, &virial9, &out_f64, &pp,
                         &check_count, &positions_out, &dest, &counts_io};
-        HTF_CHECK_HIP(hipModuleLaunchKernel(p.jit->row1v[f64][store], (batch + 3) / 4, 1, 1, 256, 1, 1, 0, s, args, nullptr));
+        HTF_CHECK_HIP(hipModuleLaunchKernel(p.jit->row1v[f64][store], fused_row1_grid(batch), 1, 1, 256, 1, 1, 0, s, args, nullptr));
     }
     return HTF_OK;
 }

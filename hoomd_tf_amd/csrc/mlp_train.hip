@@ -19,6 +19,7 @@
 #include <cstdlib>
 
 #include "htf_common.h"
+#include "dispatch.h"
 #include "htf_internal.h"
 #include "pair_mlp.h"
 
@@ -630,20 +631,11 @@ int mlp_train_grad(const MlpDevice *m, const void *nlist, int in_dtype, unsigned
         const unsigned long long units = (unsigned long long)B * ntiles;
         unsigned nblk = (unsigned)m->n_cu;
         if ((unsigned long long)nblk * 4 > units) nblk = (unsigned)((units + 3) / 4);
-#define HTF_LAUNCH_MLPM(T, IT, V4, F)                                                                                  \
-    hipLaunchKernelGGL((mlp_grad_mfma_kernel<T, IT, F>), dim3(nblk), dim3(256), 0, stream, (const V4 *)nlist, B, NN,   \
-                       labels, lab_f64, predbuf, (float4 *)pred, m->train_images, dm, m->gap, partial, stride)
-#define HTF_LAUNCH_MLPM2(T, IT, V4)                                                                                    \
-    do {                                                                                                               \
-        if (fused) HTF_LAUNCH_MLPM(T, IT, V4, true); else HTF_LAUNCH_MLPM(T, IT, V4, false);                           \
-    } while (0)
-        if (in_dtype == HTF_F32) {
-            if (th) HTF_LAUNCH_MLPM2(true, float, float4); else HTF_LAUNCH_MLPM2(false, float, float4);
-        } else {
-            if (th) HTF_LAUNCH_MLPM2(true, double, double4); else HTF_LAUNCH_MLPM2(false, double, double4);
-        }
-#undef HTF_LAUNCH_MLPM2
-#undef HTF_LAUNCH_MLPM
+        dispatch_flags([&](auto TANH, auto F64, auto FUSED) {
+            using IT = scalar_t<F64>;
+            hipLaunchKernelGGL((mlp_grad_mfma_kernel<TANH, IT, FUSED>), dim3(nblk), dim3(256), 0, stream, (const typename Vec4<IT>::type *)nlist,
+                               B, NN, labels, lab_f64, predbuf, (float4 *)pred, m->train_images, dm, m->gap, partial, stride);
+        }, th, in_dtype != HTF_F32, fused);
         rc = check_launch("mlp_grad_mfma_kernel");
         if (rc != HTF_OK) return rc;
         hipLaunchKernelGGL(mlp_reduce_partials_kernel, dim3((ncols + 63) / 64), dim3(64 * kRedSlices), 0, stream, partial, nblk, stride,
@@ -656,15 +648,11 @@ int mlp_train_grad(const MlpDevice *m, const void *nlist, int in_dtype, unsigned
                                       : m->precision == HTF_MLP_SPLIT16 ? Img<3>::TabC : Img<0>::TabC);
     const float ginv = 1.0f / m->gap;
     const dim3 grid(nw / 4), block(256);
-#define HTF_LAUNCH_MLPG(T, IT, V4)                                                                                     \
-    hipLaunchKernelGGL((mlp_grad_kernel<T, IT>), grid, block, 0, stream, (const V4 *)nlist, B, NN, labels, lab_f64,    \
-                       predbuf, m->theta, dm, tab_c, ginv, partial, stride)
-    if (in_dtype == HTF_F32) {
-        if (th) HTF_LAUNCH_MLPG(true, float, float4); else HTF_LAUNCH_MLPG(false, float, float4);
-    } else {
-        if (th) HTF_LAUNCH_MLPG(true, double, double4); else HTF_LAUNCH_MLPG(false, double, double4);
-    }
-#undef HTF_LAUNCH_MLPG
+    dispatch_flags([&](auto TANH, auto F64) {
+        using IT = scalar_t<F64>;
+        hipLaunchKernelGGL((mlp_grad_kernel<TANH, IT>), grid, block, 0, stream, (const typename Vec4<IT>::type *)nlist, B, NN, labels, lab_f64,
+                           predbuf, m->theta, dm, tab_c, ginv, partial, stride);
+    }, th, in_dtype != HTF_F32);
     rc = check_launch("mlp_grad_kernel");
     if (rc != HTF_OK) return rc;
     hipLaunchKernelGGL(mlp_reduce_partials_kernel, dim3((ncols + 63) / 64), dim3(64 * kRedSlices), 0, stream, partial, nw, stride,

@@ -5,6 +5,7 @@
 // accumulator is the exponent -- and the tangent chain is scaled back).
 // Compiled -fno-slp-vectorize: packed fp32 instructions do not run beside 16-bit MFMA work on gfx950 (tools/mfma_valu_probe2.hip).
 #include "htf_common.h"
+#include "dispatch.h"
 #include "htf_internal.h"
 #include "pair_mlp.h"
 
@@ -617,19 +618,13 @@ int mlp_train_grad16(const MlpDevice *m, const void *nlist, int in_dtype, unsign
     //  8.69 / 8.35 k with 224 / 192 / 160 / 128 on bench.py --workload mlp-train -- the whole chip it is)
     if ((unsigned long long)nblk * 4 > B) nblk = (B + 3u) / 4u;
     MlpDims dm{m->K, m->H1, m->H2, m->off_b1(), m->off_W2(), m->off_b2(), m->off_W3(), m->off_b3()};
-    const bool th = m->act == HTF_ACT_TANH;
-#define HTF_LAUNCH_TR16(T, IT, V4)                                                                                     \
-    hipLaunchKernelGGL((mlp_grad_tr16_kernel<T, IT>), dim3(nblk), dim3(256), 0, stream, (const V4 *)nlist, B, NN, labels, \
-                       lab_f64, predbuf, m->images, dm, m->gap, resid_max, partial + (size_t)win * nblk * stride, stride, win)
     // one launch per residual window (see the kernel): window `win`'s block partials behind window win - 1's
-    for (int win = 0; win < kTrainWindows; ++win) {
-        if (in_dtype == HTF_F32) {
-            if (th) HTF_LAUNCH_TR16(true, float, float4); else HTF_LAUNCH_TR16(false, float, float4);
-        } else {
-            if (th) HTF_LAUNCH_TR16(true, double, double4); else HTF_LAUNCH_TR16(false, double, double4);
-        }
-    }
-#undef HTF_LAUNCH_TR16
+    dispatch_flags([&](auto TANH, auto F64) {
+        using IT = scalar_t<F64>;
+        for (int win = 0; win < kTrainWindows; ++win)
+            hipLaunchKernelGGL((mlp_grad_tr16_kernel<TANH, IT>), dim3(nblk), dim3(256), 0, stream, (const typename Vec4<IT>::type *)nlist, B, NN,
+                               labels, lab_f64, predbuf, m->images, dm, m->gap, resid_max, partial + (size_t)win * nblk * stride, stride, win);
+    }, m->act == HTF_ACT_TANH, in_dtype != HTF_F32);
     *nblk_out = nblk;
     return check_launch("mlp_grad_tr16_kernel");
 }

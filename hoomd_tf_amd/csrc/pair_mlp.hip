@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "htf_common.h"
+#include "dispatch.h"
 #include "htf_internal.h"
 #include "pair_mlp.h"
 #include "pair_math.h"
@@ -980,43 +981,27 @@ void mlp_destroy(MlpDevice *m) {
     delete m;
 }
 
-template <bool TANH, int P>
-static int launch_mlp(const MlpDevice *m, const void *nlist, int in_dtype, unsigned B, unsigned NN, void *force,
-                      int out_f64, void *virial9, hipStream_t s) {
-    // persistent blocks: one of eight waves per CU (MlpLaunch)
-    unsigned grid = (unsigned)m->n_cu * (unsigned)MlpLaunch<P>::kPerCU;
-    constexpr unsigned kW = (unsigned)MlpLaunch<P>::kWaves;
-    unsigned need = (B + kW - 1) / kW;
-    if (grid > need) grid = need;
-#define HTF_MLP_LAUNCH(T, V4, VIR)                                                                                     \
-    hipLaunchKernelGGL((pair_mlp_kernel<TANH, T, P, VIR>), dim3(grid), dim3(64 * kW), 0, s, (const V4 *)nlist, B, NN, force, \
-                       out_f64, m->eval_images, m->gap, virial9)
-    if (in_dtype == HTF_F32) {
-        if (virial9) HTF_MLP_LAUNCH(float, float4, true); else HTF_MLP_LAUNCH(float, float4, false);
-    } else {
-        if (virial9) HTF_MLP_LAUNCH(double, double4, true); else HTF_MLP_LAUNCH(double, double4, false);
-    }
-#undef HTF_MLP_LAUNCH
-    return check_launch("pair_mlp_kernel");
-}
-
 int mlp_eval(const MlpDevice *m, const void *nlist, int in_dtype, unsigned B, unsigned NN, void *force,
              int force_dtype, void *virial9, hipStream_t stream) {
     HTF_REQUIRE(m, "pair-MLP: null potential");
     HTF_REQUIRE(!mlp_out_of_range(m), "pair-MLP: a weight of the device parameter vector left fp16's range (|2.885 w| >= 6e4) or is not a "
                                       "number: precision 'split16' cannot carry it; use 'split' or 'fp32'");
     const int out_f64 = force_dtype == HTF_F64;
-    if (m->precision == HTF_MLP_BF16)
-        return m->act == HTF_ACT_TANH ? launch_mlp<true, HTF_MLP_BF16>(m, nlist, in_dtype, B, NN, force, out_f64, virial9, stream)
-                                      : launch_mlp<false, HTF_MLP_BF16>(m, nlist, in_dtype, B, NN, force, out_f64, virial9, stream);
-    if (m->precision == HTF_MLP_SPLIT16)
-        return m->act == HTF_ACT_TANH ? launch_mlp<true, HTF_MLP_SPLIT16>(m, nlist, in_dtype, B, NN, force, out_f64, virial9, stream)
-                                      : launch_mlp<false, HTF_MLP_SPLIT16>(m, nlist, in_dtype, B, NN, force, out_f64, virial9, stream);
-    if (m->precision == HTF_MLP_SPLIT)
-        return m->act == HTF_ACT_TANH ? launch_mlp<true, HTF_MLP_SPLIT>(m, nlist, in_dtype, B, NN, force, out_f64, virial9, stream)
-                                      : launch_mlp<false, HTF_MLP_SPLIT>(m, nlist, in_dtype, B, NN, force, out_f64, virial9, stream);
-    return m->act == HTF_ACT_TANH ? launch_mlp<true, HTF_MLP_FP32>(m, nlist, in_dtype, B, NN, force, out_f64, virial9, stream)
-                                  : launch_mlp<false, HTF_MLP_FP32>(m, nlist, in_dtype, B, NN, force, out_f64, virial9, stream);
+    const auto launch = [&](auto P) {
+        // persistent blocks: one of eight waves per CU (MlpLaunch)
+        unsigned grid = (unsigned)m->n_cu * (unsigned)MlpLaunch<P>::kPerCU;
+        constexpr unsigned kW = (unsigned)MlpLaunch<P>::kWaves;
+        const unsigned need = (B + kW - 1) / kW;
+        if (grid > need) grid = need;
+        dispatch_flags([&](auto TANH, auto F64, auto VIR) {
+            using IT = scalar_t<F64>;
+            hipLaunchKernelGGL((pair_mlp_kernel<TANH, IT, P, VIR>), dim3(grid), dim3(64 * kW), 0, stream, (const typename Vec4<IT>::type *)nlist,
+                               B, NN, force, out_f64, m->eval_images, m->gap, virial9);
+        }, m->act == HTF_ACT_TANH, in_dtype != HTF_F32, virial9 != nullptr);
+    };
+    // (every other precision word is fp32)
+    if (!dispatch_value<HTF_MLP_BF16, HTF_MLP_SPLIT16, HTF_MLP_SPLIT>(launch, m->precision)) launch(std::integral_constant<int, HTF_MLP_FP32>{});
+    return check_launch("pair_mlp_kernel");
 }
 
 } // namespace htf

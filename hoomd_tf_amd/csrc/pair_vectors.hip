@@ -42,6 +42,7 @@
 
 #include "htf_common.h"
 #include "box_math.h"
+#include "dispatch.h"
 
 namespace htf {
 
@@ -244,37 +245,6 @@ __global__ __launch_bounds__(256) void build_pair_vectors_kernel(
         }
 }
 
-template <typename PT, typename DT>
-static int launch_build(void *dest, const void *pos, unsigned N, unsigned NN, unsigned offset,
-                        unsigned batch, const htf_box *hb, const unsigned *n_neigh,
-                        const unsigned *nlist, const unsigned *head_list, double rmax,
-                        unsigned *max_count, float4 *positions_out, unsigned *counts_io, hipStream_t stream) {
-    BoxT<PT> b = make_boxt<PT>(hb);
-    PT rc = (PT)rmax;
-    PT rmaxsq = rc * rc;
-    // rows per wave: 4 for fp32 positions, 2 for fp64 (4 rows spill SGPRs).  The other geometries lost their A/Bs (header of this
-    // file) and exist in variants builds only (make CXXFLAGS_EXTRA=-DHTF_AB_VARIANTS: HTF_BUILD_ROWS = 1 | 2 | 4 | 8).
-#define HTF_BUILD_LAUNCH(RR)                                                                                           \
-    hipLaunchKernelGGL((build_pair_vectors_kernel<PT, DT, RR>), dim3((batch + 4 * RR - 1) / (4 * RR)), dim3(256), 0, stream, \
-                       (typename Vec4<DT>::type *)dest, (const typename Vec4<PT>::type *)pos, N, NN, offset, batch, b, \
-                       n_neigh, nlist, head_list, rmaxsq, max_count, positions_out, counts_io)
-#ifdef HTF_AB_VARIANTS
-    static const char *rows_env = getenv("HTF_BUILD_ROWS");
-    const int rows = rows_env ? atoi(rows_env) : (sizeof(PT) == 4 ? 4 : 2);
-    if (rows == 1) HTF_BUILD_LAUNCH(1);
-    else if (rows == 4) HTF_BUILD_LAUNCH(4);
-    else if (rows == 8) HTF_BUILD_LAUNCH(8);
-    else HTF_BUILD_LAUNCH(2);
-#else
-    if constexpr (sizeof(PT) == 4) HTF_BUILD_LAUNCH(4); else HTF_BUILD_LAUNCH(2);
-#endif
-#undef HTF_BUILD_LAUNCH
-    return check_launch("build_pair_vectors_kernel");
-}
-
-} // namespace htf
-
-namespace htf {
 int build_pair_vectors_impl(void *dest, int dest_dtype, const void *d_pos, int pos_dtype, unsigned N, unsigned NN,
                             unsigned offset, unsigned batch_size, const htf_box *box, const unsigned *d_n_neigh,
                             const unsigned *d_nlist, const unsigned *d_head_list, double rmax,
@@ -286,17 +256,32 @@ int build_pair_vectors_impl(void *dest, int dest_dtype, const void *d_pos, int p
     for (int d = 0; d < 3; ++d)
         HTF_REQUIRE(box->hi[d] > box->lo[d], "htf_build_pair_vectors: empty box along %d", d);
     if (batch_size == 0) return HTF_OK;
-    if (pos_dtype == HTF_F32 && dest_dtype == HTF_F32)
-        return launch_build<float, float>(dest, d_pos, N, NN, offset, batch_size, box, d_n_neigh, d_nlist, d_head_list, rmax, d_max_count, positions_out, counts_io, s);
-    if (pos_dtype == HTF_F64 && dest_dtype == HTF_F32)
-        return launch_build<double, float>(dest, d_pos, N, NN, offset, batch_size, box, d_n_neigh, d_nlist, d_head_list, rmax, d_max_count, positions_out, counts_io, s);
-    if (pos_dtype == HTF_F64 && dest_dtype == HTF_F64)
-        return launch_build<double, double>(dest, d_pos, N, NN, offset, batch_size, box, d_n_neigh, d_nlist, d_head_list, rmax, d_max_count, positions_out, counts_io, s);
-    if (pos_dtype == HTF_F32 && dest_dtype == HTF_F64)
-        return launch_build<float, double>(dest, d_pos, N, NN, offset, batch_size, box, d_n_neigh, d_nlist, d_head_list, rmax, d_max_count, positions_out, counts_io, s);
-    set_error("htf_build_pair_vectors: bad dtype (%d, %d)", pos_dtype, dest_dtype);
-    return HTF_ERR_INVALID;
+    HTF_REQUIRE((pos_dtype == HTF_F32 || pos_dtype == HTF_F64) && (dest_dtype == HTF_F32 || dest_dtype == HTF_F64),
+                "htf_build_pair_vectors: bad dtype (%d, %d)", pos_dtype, dest_dtype);
+    dispatch_flags([&](auto P64, auto D64) {
+        using PT = scalar_t<P64>;
+        using DT = scalar_t<D64>;
+        const BoxT<PT> b = make_boxt<PT>(box);
+        const PT rc = (PT)rmax;
+        const PT rmaxsq = rc * rc;
+        const auto launch = [&](auto R) {
+            hipLaunchKernelGGL((build_pair_vectors_kernel<PT, DT, R>), dim3((batch_size + 4 * R - 1) / (4 * R)), dim3(256), 0, s,
+                               (typename Vec4<DT>::type *)dest, (const typename Vec4<PT>::type *)d_pos, N, NN, offset, batch_size, b,
+                               d_n_neigh, d_nlist, d_head_list, rmaxsq, d_max_count, positions_out, counts_io);
+        };
+        // rows per wave: 4 for fp32 positions, 2 for fp64 (4 rows spill SGPRs).  The other geometries lost their A/Bs (header of this
+        // file) and exist in variants builds only (make CXXFLAGS_EXTRA=-DHTF_AB_VARIANTS: HTF_BUILD_ROWS = 1 | 2 | 4 | 8).
+        constexpr int kRows = sizeof(PT) == 4 ? 4 : 2;
+#ifdef HTF_AB_VARIANTS
+        static const char *rows_env = getenv("HTF_BUILD_ROWS");
+        if (!dispatch_value<1, 4, 8>(launch, rows_env ? atoi(rows_env) : kRows)) launch(std::integral_constant<int, 2>{});
+#else
+        launch(std::integral_constant<int, kRows>{});
+#endif
+    }, pos_dtype == HTF_F64, dest_dtype == HTF_F64);
+    return check_launch("build_pair_vectors_kernel");
 }
+
 } // namespace htf
 
 extern "C" int htf_build_pair_vectors(void *dest, int dest_dtype, const void *d_pos, int pos_dtype,
@@ -376,18 +361,6 @@ __global__ __launch_bounds__(256) void cf_pair_kernel(int *__restrict__ dest, co
     }
 }
 
-template <typename PT>
-static int launch_pair_index(int *dest, const void *pos, unsigned NN, unsigned offset, unsigned batch, const htf_box *hb,
-                             const unsigned *n_neigh, const unsigned *nlist, const unsigned *head_list, double rmax,
-                             hipStream_t stream) {
-    BoxT<PT> b = make_boxt<PT>(hb);
-    PT rc = (PT)rmax;
-    PT rmaxsq = rc * rc;
-    hipLaunchKernelGGL((cf_pair_kernel<PT>), dim3((batch + 3) / 4), dim3(256), 0, stream, dest, (const typename Vec4<PT>::type *)pos, NN,
-                       offset, batch, b, n_neigh, nlist, head_list, rmaxsq);
-    return check_launch("cf_pair_kernel");
-}
-
 } // namespace htf
 
 extern "C" int htf_cf_pair_index(int *d_index, const void *d_pos, int pos_dtype, unsigned N, unsigned NN, unsigned offset,
@@ -402,9 +375,12 @@ extern "C" int htf_cf_pair_index(int *d_index, const void *d_pos, int pos_dtype,
         HTF_REQUIRE(box->hi[d] > box->lo[d], "htf_cf_pair_index: empty box along %d", d);
     HTF_REQUIRE(pos_dtype == HTF_F32 || pos_dtype == HTF_F64, "htf_cf_pair_index: bad dtype %d", pos_dtype);
     if (batch_size == 0) return HTF_OK;
-    if (pos_dtype == HTF_F32)
-        return launch_pair_index<float>(d_index, d_pos, NN, offset, batch_size, box, d_n_neigh, d_nlist, d_head_list, rmax,
-                                        (hipStream_t)stream);
-    return launch_pair_index<double>(d_index, d_pos, NN, offset, batch_size, box, d_n_neigh, d_nlist, d_head_list, rmax,
-                                     (hipStream_t)stream);
+    dispatch_flags([&](auto P64) {
+        using PT = scalar_t<P64>;
+        const BoxT<PT> b = make_boxt<PT>(box);
+        const PT rc = (PT)rmax;
+        hipLaunchKernelGGL((cf_pair_kernel<PT>), dim3((batch_size + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_index,
+                           (const typename Vec4<PT>::type *)d_pos, NN, offset, batch_size, b, d_n_neigh, d_nlist, d_head_list, (PT)(rc * rc));
+    }, pos_dtype != HTF_F32);
+    return check_launch("cf_pair_kernel");
 }

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "htf_common.h"
+#include "dispatch.h"
 #include "htf_internal.h"
 #include "pair_math.h"
 
@@ -270,20 +271,11 @@ int topk_eval(const TopkDevice *m, const void *nlist, int in_dtype, unsigned B, 
     const int out_f64 = force_dtype == HTF_F64;
     const unsigned grid = (B + 3) / 4;
     const size_t lds = (((size_t)m->n_floats() + 3) & ~(size_t)3) * sizeof(float) + 4 * kTopH * sizeof(float);
-#define HTF_TK(TANH, VIR, T, V4)                                                                                       \
-    hipLaunchKernelGGL((topk_mlp_kernel<TANH, VIR, T>), dim3(grid), dim3(256), lds, s, (const V4 *)nlist, B, NN, force, \
-                       virial9, out_f64, m->w, m->K, m->H1, m->H2)
-#define HTF_TK2(TANH, VIR)                                                                                             \
-    do {                                                                                                               \
-        if (in_dtype == HTF_F32) HTF_TK(TANH, VIR, float, float4); else HTF_TK(TANH, VIR, double, double4);            \
-    } while (0)
-    if (m->act == HTF_ACT_TANH) {
-        if (virial9) HTF_TK2(true, true); else HTF_TK2(true, false);
-    } else {
-        if (virial9) HTF_TK2(false, true); else HTF_TK2(false, false);
-    }
-#undef HTF_TK2
-#undef HTF_TK
+    dispatch_flags([&](auto TANH, auto VIR, auto F64) {
+        using IT = scalar_t<F64>;
+        hipLaunchKernelGGL((topk_mlp_kernel<TANH, VIR, IT>), dim3(grid), dim3(256), lds, s, (const typename Vec4<IT>::type *)nlist, B, NN,
+                           force, virial9, out_f64, m->w, m->K, m->H1, m->H2);
+    }, m->act == HTF_ACT_TANH, virial9 != nullptr, in_dtype != HTF_F32);
     return check_launch("topk_mlp_kernel");
 }
 

@@ -238,6 +238,9 @@ __global__ __launch_bounds__(256) void train_pair_kernel(const typename Vec4<IT>
 #ifdef HTF_JIT_UNIT
 } // namespace htf  (a generated unit takes the sweep above and nothing else of this file)
 #else
+} // namespace htf
+#include "dispatch.h" // (host side only)
+namespace htf {
 // accum[w] = sum_b partials[b][w]  (one block, fixed order, fp64 accumulation)
 __global__ __launch_bounds__(1024) void reduce_columns_kernel(const float *__restrict__ partials, unsigned nblocks,
                                                               unsigned width, float *__restrict__ accum) {
@@ -255,43 +258,6 @@ __global__ __launch_bounds__(1024) void reduce_columns_kernel(const float *__res
             accum[w] = (float)t;
         }
     }
-}
-
-template <int KIND>
-static int launch_train(const PotParams &p, const void *nlist, int in_dtype, unsigned B, unsigned NN,
-                        const void *labels, int lab_f64, void *pred, float *accum, float *scratch, hipStream_t s) {
-    constexpr unsigned rows_per_block = 4 * (64 / kTrainG);
-    constexpr unsigned width = 1 + NumParams<KIND>::value;
-    const unsigned grid = (B + rows_per_block - 1) / rows_per_block;
-    if (in_dtype == HTF_F32)
-        hipLaunchKernelGGL((train_pair_kernel<KIND, float>), dim3(grid), dim3(256), 0, s, (const float4 *)nlist, B, NN, labels, lab_f64, pred, p, scratch);
-    else
-        hipLaunchKernelGGL((train_pair_kernel<KIND, double>), dim3(grid), dim3(256), 0, s, (const double4 *)nlist, B, NN, labels, lab_f64, pred, p, scratch);
-    int rc = check_launch("train_pair_kernel");
-    if (rc != HTF_OK) return rc;
-    hipLaunchKernelGGL(reduce_columns_kernel, dim3(1), dim3(1024), 0, s, scratch, grid, width, accum);
-    return check_launch("reduce_columns_kernel");
-}
-
-template <int KIND>
-static int launch_train_list(const PotParams &p, const void *pos, int pos_dtype, unsigned B, unsigned NN, const htf_box *hb,
-                             const unsigned *n_neigh, const unsigned *nlist, const unsigned *head_list, double rmax,
-                             const void *labels, int lab_f64, void *pred, float *accum, float *scratch, hipStream_t s) {
-    constexpr unsigned rows_per_block = 4 * (64 / kTrainListG);
-    constexpr unsigned width = 1 + NumParams<KIND>::value;
-    const unsigned grid = (B + rows_per_block - 1) / rows_per_block;
-    if (pos_dtype == HTF_F32) {
-        const float rc = (float)rmax;
-        hipLaunchKernelGGL((train_list_kernel<KIND, float>), dim3(grid), dim3(256), 0, s, (const float4 *)pos, B, NN, make_boxt<float>(hb),
-                           n_neigh, nlist, head_list, rc * rc, labels, lab_f64, pred, p, scratch);
-    } else {
-        hipLaunchKernelGGL((train_list_kernel<KIND, double>), dim3(grid), dim3(256), 0, s, (const double4 *)pos, B, NN, make_boxt<double>(hb),
-                           n_neigh, nlist, head_list, rmax * rmax, labels, lab_f64, pred, p, scratch);
-    }
-    int rc2 = check_launch("train_list_kernel");
-    if (rc2 != HTF_OK) return rc2;
-    hipLaunchKernelGGL(reduce_columns_kernel, dim3(1), dim3(1024), 0, s, scratch, grid, width, accum);
-    return check_launch("reduce_columns_kernel");
 }
 
 int potential_num_params(const PotParams &p) {
@@ -319,50 +285,63 @@ size_t train_scratch_floats(const PotParams &p, unsigned B, unsigned NN) {
     return (size_t)((B + rows_per_block - 1) / rows_per_block) * train_width(p);
 }
 
+// the closed forms either sweep trains
+template <typename F>
+static bool dispatch_train_kind(F &&f, int kind) {
+    return dispatch_value<HTF_POT_LJ_PARAM, HTF_POT_WCA, HTF_POT_RINV_POLY>(f, kind);
+}
+
+// the end of either sweep, a closed form's or a generated unit's (csrc/jit.hip): the library's own reduction of its block partials
+static int sweep_reduce(int sweep_rc, const PotParams &p, const float *scratch, unsigned grid, float *accum, hipStream_t stream) {
+    if (sweep_rc != HTF_OK) return sweep_rc;
+    hipLaunchKernelGGL(reduce_columns_kernel, dim3(1), dim3(1024), 0, stream, scratch, grid, train_width(p), accum);
+    return check_launch("reduce_columns_kernel");
+}
+
 int train_pair_dispatch(const PotParams &p, const void *nlist, int in_dtype, unsigned B, unsigned NN,
                         const void *labels, int label_dtype, void *pred, float *accum, float *scratch,
                         hipStream_t stream) {
     const int lab_f64 = label_dtype == HTF_F64;
-    switch (p.kind) {
-    case HTF_POT_LJ_PARAM: return launch_train<HTF_POT_LJ_PARAM>(p, nlist, in_dtype, B, NN, labels, lab_f64, pred, accum, scratch, stream);
-    case HTF_POT_WCA: return launch_train<HTF_POT_WCA>(p, nlist, in_dtype, B, NN, labels, lab_f64, pred, accum, scratch, stream);
-    case HTF_POT_RINV_POLY: return launch_train<HTF_POT_RINV_POLY>(p, nlist, in_dtype, B, NN, labels, lab_f64, pred, accum, scratch, stream);
-    case HTF_POT_JIT: { // the generated unit's instantiation of the sweep above (csrc/jit.hip), then the library's own reduction
-        constexpr unsigned rows_per_block = 4 * (64 / kTrainG);
-        const unsigned grid = (B + rows_per_block - 1) / rows_per_block;
-        int rc = jit_launch_train(p, nlist, in_dtype, B, NN, labels, lab_f64, pred, scratch, grid, stream);
-        if (rc != HTF_OK) return rc;
-        hipLaunchKernelGGL(reduce_columns_kernel, dim3(1), dim3(1024), 0, stream, scratch, grid, 1u + (unsigned)p.n_terms, accum);
-        return check_launch("reduce_columns_kernel");
-    }
-    default:
+    constexpr unsigned rows_per_block = 4 * (64 / kTrainG);
+    const unsigned grid = (B + rows_per_block - 1) / rows_per_block;
+    if (p.kind == HTF_POT_JIT)
+        return sweep_reduce(jit_launch_train(p, nlist, in_dtype, B, NN, labels, lab_f64, pred, scratch, grid, stream), p, scratch, grid, accum, stream);
+    const bool closed = dispatch_train_kind([&](auto KIND) {
+        dispatch_flags([&](auto F64) {
+            using IT = scalar_t<F64>;
+            hipLaunchKernelGGL((train_pair_kernel<KIND, IT>), dim3(grid), dim3(256), 0, stream, (const typename Vec4<IT>::type *)nlist, B, NN,
+                               labels, lab_f64, pred, p, scratch);
+        }, in_dtype != HTF_F32);
+    }, p.kind);
+    if (!closed) {
         set_error("htf_train_pair_grad: potential kind %d has no trainable closed form (pair-MLP training: next round)", p.kind);
         return HTF_ERR_INVALID;
     }
+    return sweep_reduce(check_launch("train_pair_kernel"), p, scratch, grid, accum, stream);
 }
 
 int train_list_dispatch(const PotParams &p, const void *pos, int pos_dtype, unsigned B, unsigned NN, const htf_box *box,
                         const unsigned *n_neigh, const unsigned *nlist, const unsigned *head_list, double rmax, const void *labels,
                         int label_dtype, void *pred, float *accum, float *scratch, hipStream_t stream) {
     const int lab_f64 = label_dtype == HTF_F64;
-#define HTF_TL(K) launch_train_list<K>(p, pos, pos_dtype, B, NN, box, n_neigh, nlist, head_list, rmax, labels, lab_f64, pred, accum, scratch, stream)
-    switch (p.kind) {
-    case HTF_POT_LJ_PARAM: return HTF_TL(HTF_POT_LJ_PARAM);
-    case HTF_POT_WCA: return HTF_TL(HTF_POT_WCA);
-    case HTF_POT_RINV_POLY: return HTF_TL(HTF_POT_RINV_POLY);
-    case HTF_POT_JIT: {
-        constexpr unsigned rows_per_block = 4 * (64 / kTrainListG);
-        const unsigned grid = (B + rows_per_block - 1) / rows_per_block;
-        int rc = jit_launch_train_list(p, pos, pos_dtype, B, NN, box, n_neigh, nlist, head_list, rmax, labels, lab_f64, pred, scratch, grid, stream);
-        if (rc != HTF_OK) return rc;
-        hipLaunchKernelGGL(reduce_columns_kernel, dim3(1), dim3(1024), 0, stream, scratch, grid, 1u + (unsigned)p.n_terms, accum);
-        return check_launch("reduce_columns_kernel");
-    }
-    default:
+    constexpr unsigned rows_per_block = 4 * (64 / kTrainListG);
+    const unsigned grid = (B + rows_per_block - 1) / rows_per_block;
+    if (p.kind == HTF_POT_JIT)
+        return sweep_reduce(jit_launch_train_list(p, pos, pos_dtype, B, NN, box, n_neigh, nlist, head_list, rmax, labels, lab_f64, pred, scratch, grid, stream),
+                            p, scratch, grid, accum, stream);
+    const bool closed = dispatch_train_kind([&](auto KIND) {
+        dispatch_flags([&](auto F64) {
+            using PT = scalar_t<F64>;
+            const PT rc = (PT)rmax;
+            hipLaunchKernelGGL((train_list_kernel<KIND, PT>), dim3(grid), dim3(256), 0, stream, (const typename Vec4<PT>::type *)pos, B, NN,
+                               make_boxt<PT>(box), n_neigh, nlist, head_list, rc * rc, labels, lab_f64, pred, p, scratch);
+        }, pos_dtype != HTF_F32);
+    }, p.kind);
+    if (!closed) {
         set_error("htf_train_pair_grad_list: potential kind %d has no list-form training sweep (the pair-MLP's reads the tensor)", p.kind);
         return HTF_ERR_INVALID;
     }
-#undef HTF_TL
+    return sweep_reduce(check_launch("train_list_kernel"), p, scratch, grid, accum, stream);
 }
 
 // tf.keras.optimizers.{SGD, Adam, Nadam} (TF 2.3/2.4 optimizer_v2 update rules)

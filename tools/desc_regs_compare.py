@@ -8,7 +8,10 @@ SIMD, or is missing from either.
 Waves per SIMD are those the registers allow: min(8, 512 // alloc), alloc = VGPRs rounded up to the granule of 8.  That covers
 the sweeps' __launch_bounds__(256, 1) -- a form above 256 registers gets 1 -- but not LDS: the family's LDS is dynamic (the
 notes' static size is 0 for every kernel) and a function of the call's widths alone, which no change to a kernel body moves.
-usage: tools/desc_regs_compare.py BEFORE.so AFTER.so [--all]"""
+--family REGEX compares another family: the kernels whose name (without ``htf::``) the expression matches at its start, e.g. the
+pair path's 'fused_|eval_pair|pair_mlp|mlp_grad|mlp_re|topk_|train_|build_pair|cf_pair|nlist_rinv|check_nlist|reduce_|bias_combine|optimizer_'.
+usage: tools/desc_regs_compare.py BEFORE.so AFTER.so [--all] [--family REGEX]"""
+import argparse
 import pathlib
 import re
 import struct
@@ -17,7 +20,7 @@ import sys
 import tempfile
 
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-FAMILY = re.compile(r"^htf::(bp_|dtrain|cf_|ct_|ang_|at_|cmt_|committee_)")
+FAMILY = "bp_|dtrain|cf_|ct_|ang_|at_|cmt_|committee_"
 KEYS = ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count", "group_segment_fixed_size")
 
 
@@ -25,7 +28,7 @@ def waves(vgprs):
     return min(8, 512 // (-(-vgprs // 8) * 8))
 
 
-def family(lib):
+def family(lib, regex=FAMILY):
     """{kernel: {key: value}} of the family's kernels in the gfx950 code objects bundled into lib (the walk of
     tests/test_codeobj.py, with the keys wanted here)."""
     data = pathlib.Path(lib).read_bytes()
@@ -51,16 +54,23 @@ def family(lib):
     names = sorted(meta)
     dem = subprocess.run(["c++filt"] + names, capture_output=True, text=True, check=True).stdout.strip().split("\n")
     out = {}
+    want = re.compile(r"^htf::(%s)" % regex)
     for n, d in zip(names, dem):
         short = d.replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "")
-        if FAMILY.match(short):
+        if want.match(short):
             out[short[5:]] = meta[n]
     return out
 
 
 def main():
-    show_all = "--all" in sys.argv
-    before, after = (family(p) for p in [a for a in sys.argv[1:] if a != "--all"][:2])
+    ap = argparse.ArgumentParser(usage=__doc__)
+    ap.add_argument("before")
+    ap.add_argument("after")
+    ap.add_argument("--all", action="store_true")
+    ap.add_argument("--family", default=FAMILY, metavar="REGEX")
+    a = ap.parse_args()
+    show_all = a.all
+    before, after = family(a.before, a.family), family(a.after, a.family)
     bad = sorted(set(before) ^ set(after))
     same = 0
     print("| kernel | VGPRs | waves/SIMD | SGPRs | scratch + VGPR spills | SGPR spills | LDS |")

@@ -15,7 +15,9 @@ rows, with the ghost particles' table rows from their owners: include/htf_cghost
 ``DescriptorMLP(conservative=True, n_models=M)``, whose ``total_forces`` gives the mean-model forces and leaves the per-particle
 model deviation in ``layer.deviation``, the descriptor and every exponential formed once for all members: include/htf_committee.h;
 ``trainable="committee"`` trains that committee where it runs, ``committee_loss_gradient`` being the force-matching sweep of all
-M members at once, one wave per member on the same rows: include/htf_cmt_train.h).
+M members at once, one wave per member on the same rows: include/htf_cmt_train.h; hidden layers up to 256 wide for the
+conservative forces, ``DescriptorMLP(conservative=True, dense="mfma")``, the dense stack of a 64-row tile on the fp32 matrix
+instruction: include/htf_cfwide.h).
 The offline path ``iter_from_trajectory`` / ``ArrayTrajectory`` runs a
 ``SimModel`` over stored frames.
 ``DeviationSelector`` consumes the committee's deviation where it is produced: ``sel.update(layer.deviation, positions, box)``

@@ -327,6 +327,12 @@ CMT_TRAIN_PROTOTYPES = {
     "htf_cmt_loss_grad": (_i, CT_PROTOTYPES["htf_ct_loss_grad"][1][:-1] + [_u, _u, _u, _vp]),
 }
 
+# pass 1 of the conservative forces on the fp32 matrix instruction (include/htf_cfwide.h; DescriptorMLP(dense="mfma")):
+# htf_cf_grad's arguments, hidden widths up to 256
+CFW_PROTOTYPES = {
+    "htf_cfw_grad": (_i, list(CF_PROTOTYPES["htf_cf_grad"][1])),
+}
+
 # frame selection by committee deviation (include/htf_select.h; hoomd_tf_amd/select.py DeviationSelector)
 SEL_FIRST, SEL_LARGEST = 0, 1
 SEL_FORCE, SEL_ENERGY = 0, 1
@@ -341,7 +347,7 @@ SEL_PROTOTYPES = {
 # every table above: what the ctypes and the pybind11 binding both declare
 ALL_PROTOTYPES = tuple((name, proto) for table in (PROTOTYPES, STANDIN_PROTOTYPES, STEP_CHECK_PROTOTYPES, CG_PROTOTYPES, GEOM_PROTOTYPES, NLIST_PROTOTYPES,
                                                    BP_PROTOTYPES, CF_PROTOTYPES, CT_PROTOTYPES, ANG_PROTOTYPES, AT_PROTOTYPES, CGHOST_PROTOTYPES,
-                                                   CMT_PROTOTYPES, CMT_TRAIN_PROTOTYPES, SEL_PROTOTYPES)
+                                                   CMT_PROTOTYPES, CMT_TRAIN_PROTOTYPES, SEL_PROTOTYPES, CFW_PROTOTYPES)
                        for name, proto in table.items())
 
 

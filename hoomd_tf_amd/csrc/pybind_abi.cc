@@ -26,6 +26,7 @@
 #include "htf_atrain.h"
 #include "htf_cghost.h"
 #include "htf_select.h"
+#include "htf_cfwide.h"
 
 namespace py = pybind11;
 
@@ -236,6 +237,10 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
     X(htf_sel_update) \
     X(htf_sel_reset)
 
+// include/htf_cfwide.h: pass 1 of the conservative forces on the fp32 matrix instruction (_lib.CFW_PROTOTYPES)
+#define HTF_CFW_FUNCTIONS(X) \
+    X(htf_cfw_grad)
+
 PYBIND11_MODULE(_htf_abi, m) {
     m.doc() = "pybind11 binding of libhtf_amd.so's C ABI: pointers as integers";
     // a stale module (or library): this module's templates were instantiated from one header, the library it resolved at load
@@ -259,5 +264,6 @@ PYBIND11_MODULE(_htf_abi, m) {
     HTF_CMT_FUNCTIONS(X)
     HTF_CMT_TRAIN_FUNCTIONS(X)
     HTF_SEL_FUNCTIONS(X)
+    HTF_CFW_FUNCTIONS(X)
 #undef X
 }

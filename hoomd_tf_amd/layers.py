@@ -394,19 +394,34 @@ class DescriptorMLP:
     with its own optimizer state; the loss metric reads the mean of the members' losses.  The sweep keeps all M networks and
     six exchange lines and 256 slot terms per member in LDS, ``4 (M (P4 + 640) + K4)`` bytes; above 160 KiB the constructor raises.  In the run,
     ``n_species > 1``, several ranks and batches raise; offline the method covers species.
-    Limits: ``n_types * K * (1 + l_max) <= 64``, ``H1, H2 <= 64``, at most 256 neighbor slots."""
+    ``dense="mfma"`` (with ``conservative=True``; htf_cfw_grad, include/htf_cfwide.h) lifts the hidden widths to ``1 <= H1, H2 <=
+    256``, the widths of Behler-Parrinello, ANI and DeepMD fitting networks.  The default ``dense="lanes"`` keeps one hidden unit
+    per lane of the wave that owns a row and so ends at 64.  With ``"mfma"`` the first sweep of ``total_forces`` works on tiles of
+    64 rows: the waves of a block form the rows' ``G_i`` by the row kernel's own sums (the same bits), then the forward and the
+    backward of the whole tile run as ``v_mfma_f32_32x32x2_f32`` products in exact fp32, the activations in LDS and the weights
+    streamed from L2 as they lie in ``w``.  It writes the same ``g`` and ``E`` tables, so the second sweep, ``n_species``,
+    ``n_ghost`` / ``halo``, ``compute_nlist_forces`` and ``tfcompute`` work unchanged; forces and energies agree with
+    ``dense="lanes"`` to rounding (the sums over hidden units run in the matrix unit's order), not bit for bit.  ``w``, the
+    initial weights and the weights API are the same.  Not covered, each raising: ``l_max > 0``, ``n_models > 1``, any
+    ``trainable`` value, and ``forces`` / ``loss_gradient`` / ``total_loss_gradient``, whose kernels keep one unit per lane;
+    ``descriptor`` is independent of the network and works.  Timings of both stacks at equal widths: DESIGN.md 0.12.
+    Limits: ``n_types * K * (1 + l_max) <= 64``, ``H1, H2 <= 64`` (256 with ``dense="mfma"``), at most 256 neighbor slots."""
 
     name = 'descriptor-mlp'
     _KEYS = ("W1", "b1", "W2", "b2", "W3", "b3")
     MAX_D, MAX_H, MAX_NN = 64, 64, 256
+    MAX_H_MFMA = 256                                # include/htf_cfwide.h
     MAX_MODELS, MAX_COMMITTEE_LDS = 8, 160 * 1024   # include/htf_committee.h
     deviation = None    # a committee's (devF_i, devE_i) [B, 2] of its last total_forces call
     nonneg_mask = 0     # what the optimizer step reads of a trainable layer: no weight is constrained or regularised
     l1_reg = (0.0,)
 
     def __init__(self, K=16, H1=32, H2=32, low=0.0, high=3.0, n_types=1, activation="tanh", seed=3, device=None,
-                 trainable=False, r_cut=None, n_species=1, conservative=False, l_max=0, n_models=1):
+                 trainable=False, r_cut=None, n_species=1, conservative=False, l_max=0, n_models=1, dense="lanes"):
         K, H1, H2, n_types, n_species = int(K), int(H1), int(H2), int(n_types), int(n_species)
+        if dense not in ("lanes", "mfma"):
+            raise ValueError("DescriptorMLP: dense must be 'lanes' or 'mfma', not %r" % (dense,))
+        self.dense = dense
         if isinstance(l_max, bool) or int(l_max) != l_max or int(l_max) not in (0, 1, 2):
             raise ValueError("DescriptorMLP: l_max must be 0, 1 or 2, not %r" % (l_max,))
         self.l_max = l_max = int(l_max)
@@ -474,8 +489,20 @@ class DescriptorMLP:
         if n_types * K * (1 + l_max) > self.MAX_D:
             raise ValueError("DescriptorMLP: n_types * K * (1 + l_max) = %d * %d * %d network inputs; the kernel takes 1 to %d"
                              % (n_types, K, 1 + l_max, self.MAX_D))
-        if not (1 <= H1 <= self.MAX_H and 1 <= H2 <= self.MAX_H):
-            raise ValueError("DescriptorMLP: hidden widths %d, %d outside [1, %d]" % (H1, H2, self.MAX_H))
+        if dense == "mfma":
+            if not self.conservative:
+                raise ValueError("DescriptorMLP: dense=\"mfma\" needs conservative=True: it is the first sweep of total_forces "
+                                 "(include/htf_cfwide.h); the row operator has no MFMA form")
+            if l_max or n_models > 1 or self.trainable:
+                raise ValueError("DescriptorMLP: dense=\"mfma\" does not go with %s: the angular, committee and force-matching "
+                                 "sweeps keep one hidden unit per lane; dense=\"lanes\" with H1, H2 <= %d runs them"
+                                 % ("l_max = %d" % l_max if l_max else "n_models = %d" % n_models if n_models > 1
+                                    else "trainable=%r" % (trainable,), self.MAX_H))
+        max_h = self.MAX_H_MFMA if dense == "mfma" else self.MAX_H
+        if not (1 <= H1 <= max_h and 1 <= H2 <= max_h):
+            raise ValueError("DescriptorMLP: hidden widths %d, %d outside [1, %d]%s" % (
+                H1, H2, max_h, "" if dense == "mfma" else
+                "; conservative=True with dense=\"mfma\" takes up to %d" % self.MAX_H_MFMA))
         rbf = RBFExpansion(low, high, K)
         if not rbf.gap > 0:
             raise ValueError("DescriptorMLP: high = %g must exceed low = %g" % (rbf.high, rbf.low))
@@ -535,6 +562,12 @@ class DescriptorMLP:
         lay.mu = self.mu
         return lay
 
+    def _no_mfma(self, what):
+        if self.dense == "mfma":
+            raise NotImplementedError("DescriptorMLP: %s() keeps one hidden unit per lane and has no MFMA form (dense=\"mfma\"): "
+                                      "total_forces(x, index) evaluates this layer; dense=\"lanes\" with H1, H2 <= %d has %s()"
+                                      % (what, self.MAX_H, what))
+
     def _no_committee(self, what):
         if self.n_models > 1:
             raise NotImplementedError("DescriptorMLP: %s() is a single network's; on a committee (n_models = %d) member(m).%s() "
@@ -556,6 +589,8 @@ class DescriptorMLP:
             cfg['l_max'] = self.l_max
         if self.n_models != 1:
             cfg['n_models'] = self.n_models
+        if self.dense != "lanes":
+            cfg['dense'] = self.dense
         return cfg
 
     def get_weights(self):
@@ -677,6 +712,7 @@ class DescriptorMLP:
         [B, 4] (column 3), needed when ``n_species > 1``."""
         self._no_angular("forces")
         self._no_committee("forces")
+        self._no_mfma("forces")
         a = self._Args(self, x)
         out = torch.empty((a.B, 4), dtype=x.dtype, device=x.device)
         v = torch.empty((a.B, 3, 3), dtype=x.dtype, device=x.device) if virial else None
@@ -772,6 +808,9 @@ class DescriptorMLP:
             grad, forces, e = lib.htf_ang_grad, lib.htf_ang_forces_ghost, f32(B)
             table = f32(B + n_ghost, self.Dr, 4 if self.l_max == 1 else 10)
             own1, own2 = (self.l_max,), (self.l_max, B + n_ghost)
+        elif self.dense == "mfma":   # include/htf_cfwide.h: pass 1 on the matrix instruction, the same table; pass 2 as below
+            grad, forces, table, e = lib.htf_cfw_grad, lib.htf_cf_forces_ghost, f32(B + n_ghost, self.D), f32(B)
+            own1, own2 = (), (B + n_ghost,)
         else:            # include/htf_cforce.h; pass 2 by include/htf_cghost.h, whose n_table = B is the plain entry
             grad, forces, table, e = lib.htf_cf_grad, lib.htf_cf_forces_ghost, f32(B + n_ghost, self.D), f32(B)
             own1, own2 = (), (B + n_ghost,)
@@ -797,6 +836,7 @@ class DescriptorMLP:
         ``s``'s rows, zeros when it has none; each row steps its own slice of ``w``."""
         self._no_angular("loss_gradient")
         self._no_committee("loss_gradient")
+        self._no_mfma("loss_gradient")
         a = self._Args(self, x)
         pred, accum, launches, rows, scratch = self._sweep_buffers(x, labels, pred, accum, species,
                                                                    lambda: self.forces(x, species=species))
@@ -870,6 +910,7 @@ class DescriptorMLP:
         with the same ``n_ghost`` and ``halo``.  ``accum`` then holds this domain's rows' share: the sum over the domains is the
         whole system's sweep."""
         self._no_committee("total_loss_gradient")
+        self._no_mfma("total_loss_gradient")
         if self.l_max:
             raise NotImplementedError("DescriptorMLP: total_loss_gradient() is the sweep of an l_max = 0 layer; with l_max = %d its "
                                       "follow-up angular_loss_gradient(x, labels, index) is the force-matching sweep" % self.l_max)

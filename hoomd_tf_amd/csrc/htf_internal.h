@@ -67,6 +67,22 @@ __device__ __forceinline__ void step_epilogue_mail(const StepEpilogue<T> *ep) {
     *reinterpret_cast<volatile unsigned long long *>(ep->mail_dst) = w;
 }
 
+// A word of the descriptor as a SCALAR register before a lane chooses among three of them.  Left to itself the compiler turns
+//   comp == 0 ? ep.lo[0] : (comp == 1 ? ep.lo[1] : ep.lo[2])
+// into ONE vector load from a per-lane address -- in the row-group forms four of them (lo, L, Linv, periodic) behind the last row's stores, and a full
+// s_waitcnt vmcnt(0) in front of the wrap: the loads and stores of gfx950 share one counter, retired in issue order, so every
+// wave waited there for the write acknowledge of all its streaming tensor stores.  Scalar loads return on lgkmcnt.
+template <typename T>
+__device__ __forceinline__ T scalar_word(T x) {
+    asm("" : "+s"(x));
+    return x;
+}
+template <typename T>
+__device__ __forceinline__ T pick3(unsigned comp, const T (&a)[3]) {
+    const T a0 = scalar_word(a[0]), a1 = scalar_word(a[1]), a2 = scalar_word(a[2]);
+    return comp == 0u ? a0 : (comp == 1u ? a1 : a2);
+}
+
 // `comp` (0..3) is the component this lane holds in `tot` (wave_sum4's lanes 0 / 16 / 32 / 48); `own` = x, y, z or w of the row's
 // own position.  standin_gate.h nve_advance + wrap1 and brick.hip shifted(), one component at a time: the same bits.
 // ``v``: the row's velocity component, loaded by the caller -- EARLY, at the head of the wave's work, by the row-group forms: a
@@ -78,10 +94,10 @@ __device__ __forceinline__ T step_epilogue_core(const StepEpilogue<T> &ep, unsig
     T *pn = reinterpret_cast<T *>(ep.pos_next) + (size_t)idx * 4;
     T xn = own; // (the type word travels as it is)
     if (comp < 3u) {
-        const T lo = comp == 0u ? ep.lo[0] : (comp == 1u ? ep.lo[1] : ep.lo[2]);
-        const T L = comp == 0u ? ep.L[0] : (comp == 1u ? ep.L[1] : ep.L[2]);
-        const T Linv = comp == 0u ? ep.Linv[0] : (comp == 1u ? ep.Linv[1] : ep.Linv[2]);
-        const int per = comp == 0u ? ep.periodic[0] : (comp == 1u ? ep.periodic[1] : ep.periodic[2]);
+        const T lo = pick3(comp, ep.lo);
+        const T L = pick3(comp, ep.L);
+        const T Linv = pick3(comp, ep.Linv);
+        const int per = pick3(comp, ep.periodic);
         const T f = (T)tot;
         v += ep.dt * f;
         xn = own + ep.dt * v;
@@ -103,7 +119,7 @@ __device__ __forceinline__ void step_epilogue_msg(const StepEpilogue<T> &ep, uns
     if (slot == 0xFFFFFFFFu) return;
     T q = xn;
     if (comp < 3u) {
-        const T sh = comp == 0u ? ep.shift[M][0] : (comp == 1u ? ep.shift[M][1] : ep.shift[M][2]);
+        const T sh = pick3(comp, ep.shift[M]);
         if (sh != (T)0) q = xn + sh;
     }
     if (ep.send != nullptr) reinterpret_cast<T *>(ep.send)[(size_t)(ep.ghost_off[M] + slot) * 4 + comp] = q;

@@ -333,6 +333,13 @@ CFW_PROTOTYPES = {
     "htf_cfw_grad": (_i, list(CF_PROTOTYPES["htf_cf_grad"][1])),
 }
 
+# force matching on the conservative forces on the fp32 matrix instruction (include/htf_cfwtrain.h;
+# DescriptorMLP.wide_loss_gradient, trainable="wide"): htf_ct_loss_grad's arguments, hidden widths up to 256
+CFWT_PROTOTYPES = {
+    "htf_cfw_scratch_floats": (C.c_size_t, [_u, _u, _u, _u, _u]),
+    "htf_cfw_loss_grad": (_i, list(CT_PROTOTYPES["htf_ct_loss_grad"][1])),
+}
+
 # frame selection by committee deviation (include/htf_select.h; hoomd_tf_amd/select.py DeviationSelector)
 SEL_FIRST, SEL_LARGEST = 0, 1
 SEL_FORCE, SEL_ENERGY = 0, 1
@@ -347,7 +354,7 @@ SEL_PROTOTYPES = {
 # every table above: what the ctypes and the pybind11 binding both declare
 ALL_PROTOTYPES = tuple((name, proto) for table in (PROTOTYPES, STANDIN_PROTOTYPES, STEP_CHECK_PROTOTYPES, CG_PROTOTYPES, GEOM_PROTOTYPES, NLIST_PROTOTYPES,
                                                    BP_PROTOTYPES, CF_PROTOTYPES, CT_PROTOTYPES, ANG_PROTOTYPES, AT_PROTOTYPES, CGHOST_PROTOTYPES,
-                                                   CMT_PROTOTYPES, CMT_TRAIN_PROTOTYPES, SEL_PROTOTYPES, CFW_PROTOTYPES)
+                                                   CMT_PROTOTYPES, CMT_TRAIN_PROTOTYPES, SEL_PROTOTYPES, CFW_PROTOTYPES, CFWT_PROTOTYPES)
                        for name, proto in table.items())
 
 

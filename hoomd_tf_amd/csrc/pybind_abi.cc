@@ -27,6 +27,7 @@
 #include "htf_cghost.h"
 #include "htf_select.h"
 #include "htf_cfwide.h"
+#include "htf_cfwtrain.h"
 
 namespace py = pybind11;
 
@@ -241,6 +242,11 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
 #define HTF_CFW_FUNCTIONS(X) \
     X(htf_cfw_grad)
 
+// include/htf_cfwtrain.h: force matching on the conservative forces on the fp32 matrix instruction (_lib.CFWT_PROTOTYPES)
+#define HTF_CFWT_FUNCTIONS(X) \
+    X(htf_cfw_scratch_floats) \
+    X(htf_cfw_loss_grad)
+
 PYBIND11_MODULE(_htf_abi, m) {
     m.doc() = "pybind11 binding of libhtf_amd.so's C ABI: pointers as integers";
     // a stale module (or library): this module's templates were instantiated from one header, the library it resolved at load
@@ -265,5 +271,6 @@ PYBIND11_MODULE(_htf_abi, m) {
     HTF_CMT_TRAIN_FUNCTIONS(X)
     HTF_SEL_FUNCTIONS(X)
     HTF_CFW_FUNCTIONS(X)
+    HTF_CFWT_FUNCTIONS(X)
 #undef X
 }

@@ -402,9 +402,20 @@ class DescriptorMLP:
     streamed from L2 as they lie in ``w``.  It writes the same ``g`` and ``E`` tables, so the second sweep, ``n_species``,
     ``n_ghost`` / ``halo``, ``compute_nlist_forces`` and ``tfcompute`` work unchanged; forces and energies agree with
     ``dense="lanes"`` to rounding (the sums over hidden units run in the matrix unit's order), not bit for bit.  ``w``, the
-    initial weights and the weights API are the same.  Not covered, each raising: ``l_max > 0``, ``n_models > 1``, any
-    ``trainable`` value, and ``forces`` / ``loss_gradient`` / ``total_loss_gradient``, whose kernels keep one unit per lane;
-    ``descriptor`` is independent of the network and works.  Timings of both stacks at equal widths: DESIGN.md 0.12.
+    initial weights and the weights API are the same.  Not covered, each raising: ``l_max > 0``, ``n_models > 1``, every
+    ``trainable`` value but ``"wide"``, and ``forces`` / ``loss_gradient`` / ``total_loss_gradient``, whose kernels keep one unit
+    per lane; ``descriptor`` is independent of the network and works.  Timings of both stacks at equal widths: DESIGN.md 0.12.
+
+    ``trainable="wide"`` (htf_cfw_loss_grad, include/htf_cfwtrain.h) is force matching on the wide stack and implies
+    ``conservative=True`` and ``dense="mfma"``, widths up to 256: under ``tfcompute.attach(..., train=True)`` every step is one
+    ``wide_loss_gradient`` sweep on the step's own list, index and ``total_forces`` output, and one optimizer step (one per
+    species present with ``n_species > 1``); offline, ``wide_loss_gradient(x, labels, index)`` with ``iter_from_trajectory``.
+    The sweep is ``total_loss_gradient``'s on tiles of 32 rows: (value | tangent) in the two halves of the three LDS images,
+    forward and reverse as matrix products, ``dW2`` and ``dW1`` as outer products of the images, each block adding its tiles
+    into a partial of its own -- no atomics, the same bits at every call.  It is callable on any single-network ``l_max = 0``
+    layer; up to 64 units ``total_loss_gradient`` (``dense="lanes"``) is the faster sweep.  Not covered on
+    the wide stack: angular channels, committees, slab domains (``n_ghost``; a ``SlabDomain`` run raises), and the row-operator
+    sweep ``loss_gradient``.
     Limits: ``n_types * K * (1 + l_max) <= 64``, ``H1, H2 <= 64`` (256 with ``dense="mfma"``), at most 256 neighbor slots."""
 
     name = 'descriptor-mlp'
@@ -419,6 +430,9 @@ class DescriptorMLP:
     def __init__(self, K=16, H1=32, H2=32, low=0.0, high=3.0, n_types=1, activation="tanh", seed=3, device=None,
                  trainable=False, r_cut=None, n_species=1, conservative=False, l_max=0, n_models=1, dense="lanes"):
         K, H1, H2, n_types, n_species = int(K), int(H1), int(H2), int(n_types), int(n_species)
+        wide = isinstance(trainable, str) and trainable == "wide"
+        if wide:
+            dense = "mfma"   # the sweep of the wide stack, fitted and run alike (include/htf_cfwtrain.h)
         if dense not in ("lanes", "mfma"):
             raise ValueError("DescriptorMLP: dense must be 'lanes' or 'mfma', not %r" % (dense,))
         self.dense = dense
@@ -453,8 +467,8 @@ class DescriptorMLP:
                 raise ValueError("DescriptorMLP: n_models = %d needs conservative=True: the deviation is defined on the forces "
                                  "of the total energy (total_forces)" % n_models)
         if isinstance(trainable, str):
-            if trainable not in ("total", "angular", "committee"):
-                raise ValueError("DescriptorMLP: trainable must be False, True, 'total', 'angular' or 'committee', not %r"
+            if trainable not in ("total", "angular", "committee", "wide"):
+                raise ValueError("DescriptorMLP: trainable must be False, True, 'total', 'angular', 'committee' or 'wide', not %r"
                                  % (trainable,))
             if trainable == "angular" and not l_max:
                 raise ValueError("DescriptorMLP: trainable=\"angular\" fits the angular channels and needs l_max = 1 or 2; "
@@ -493,7 +507,7 @@ class DescriptorMLP:
             if not self.conservative:
                 raise ValueError("DescriptorMLP: dense=\"mfma\" needs conservative=True: it is the first sweep of total_forces "
                                  "(include/htf_cfwide.h); the row operator has no MFMA form")
-            if l_max or n_models > 1 or self.trainable:
+            if l_max or n_models > 1 or (self.trainable and not wide):
                 raise ValueError("DescriptorMLP: dense=\"mfma\" does not go with %s: the angular, committee and force-matching "
                                  "sweeps keep one hidden unit per lane; dense=\"lanes\" with H1, H2 <= %d runs them"
                                  % ("l_max = %d" % l_max if l_max else "n_models = %d" % n_models if n_models > 1
@@ -578,7 +592,7 @@ class DescriptorMLP:
         cfg = {'K': self.K, 'H1': self.H1, 'H2': self.H2, 'low': self.low, 'high': self.high, 'n_types': self.n_types,
                'activation': self.activation}
         if self.trainable:
-            cfg['trainable'] = self.trainable   # (True, "total", "angular" or "committee")
+            cfg['trainable'] = self.trainable   # (True, "total", "angular", "committee" or "wide")
         if self.r_cut is not None:
             cfg['r_cut'] = self.r_cut
         if self.n_species != 1:
@@ -947,6 +961,31 @@ class DescriptorMLP:
         if self.l_max:
             return self._sweep(lib.htf_at_loss_grad_ghost, a, index, rho, buffers, (self.l_max, n_table))
         return self._sweep(lib.htf_ct_loss_grad_ghost, a, index, rho, buffers, (n_table,))
+
+    def wide_loss_gradient(self, x, labels, index, types=None, pred=None, accum=None, species=None):
+        """``total_loss_gradient`` with the dense stack on the fp32 matrix instruction (htf_cfw_loss_grad,
+        include/htf_cfwtrain.h): one force-matching sweep on the forces of the total energy for hidden layers up to 256 wide.
+        Argument for argument the same, without ghost rows: ``accum`` [1 + P], or [S, 1 + P] with zero rows for absent species,
+        holds {SSR, d SSR / d theta} per network for the residuals of ``total_forces(x, index, ...)`` against ``labels`` [B, 4];
+        ``pred`` [B, 4] fp32 is ``total_forces`` at the current weights, evaluated here (with ``types``) when not given; the
+        residual is formed in fp32 with torch and every row's is read; a slot whose index is outside ``[0, B)`` has no reverse
+        term.  Tiles of 32 rows: forward with tangent and reverse run as ``v_mfma_f32_32x32x2_f32`` products, the gradients of
+        the two weight matrices as outer products of the tile's LDS images.  Two calls on the same inputs give the same bits;
+        the result agrees with ``total_loss_gradient``'s to rounding, not bit for bit.  Callable on any single-network
+        ``l_max = 0`` layer, whatever its ``dense`` and ``trainable``; angular channels, committees and slab domains are not
+        covered."""
+        self._no_committee("wide_loss_gradient")
+        if self.l_max:
+            raise NotImplementedError("DescriptorMLP: wide_loss_gradient() is the sweep of an l_max = 0 layer; with l_max = %d "
+                                      "angular_loss_gradient(x, labels, index) is the force-matching sweep (dense=\"lanes\")"
+                                      % self.l_max)
+        a = self._Args(self, x)
+        index = self._slot_index(index, x)
+        buffers = self._sweep_buffers(
+            x, labels, pred, accum, species, lambda: self.total_forces(x, index, types=types, species=species),
+            scratch_floats=lambda n: lib.htf_cfw_scratch_floats(n, self.K, self.n_types, self.H1, self.H2))
+        rho = torch.sub(buffers[0].detach(), labels.detach().to(torch.float32)).contiguous()
+        return self._sweep(lib.htf_cfw_loss_grad, a, index, rho, buffers, ())
 
     def committee_loss_gradient(self, x, labels, index, types=None, pred=None, accum=None, species=None):
         """``total_loss_gradient`` for every member of a committee in one sweep (htf_cmt_loss_grad, include/htf_cmt_train.h):

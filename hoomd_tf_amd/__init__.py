@@ -17,7 +17,8 @@ model deviation in ``layer.deviation``, the descriptor and every exponential for
 ``trainable="committee"`` trains that committee where it runs, ``committee_loss_gradient`` being the force-matching sweep of all
 M members at once, one wave per member on the same rows: include/htf_cmt_train.h; hidden layers up to 256 wide for the
 conservative forces, ``DescriptorMLP(conservative=True, dense="mfma")``, the dense stack of a 64-row tile on the fp32 matrix
-instruction: include/htf_cfwide.h; force matching for those networks, ``DescriptorMLP(trainable="wide")`` and
+instruction: include/htf_cfwide.h, and ``dense="split16"``, the same tile on the fp16 matrix instruction with operands split as
+hi + lo: include/htf_cfwide16.h; force matching for those networks, ``DescriptorMLP(trainable="wide")`` and
 ``wide_loss_gradient``, the sweep of a 32-row tile with (value | tangent) images on the same instruction: include/htf_cfwtrain.h).
 The offline path ``iter_from_trajectory`` / ``ArrayTrajectory`` runs a
 ``SimModel`` over stored frames.

@@ -340,6 +340,12 @@ CFWT_PROTOTYPES = {
     "htf_cfw_loss_grad": (_i, list(CT_PROTOTYPES["htf_ct_loss_grad"][1])),
 }
 
+# the same pass 1 on the fp16 matrix instruction with split operands (include/htf_cfwide16.h; DescriptorMLP(dense="split16")):
+# htf_cfw_grad's arguments
+CFW16_PROTOTYPES = {
+    "htf_cfw16_grad": (_i, list(CF_PROTOTYPES["htf_cf_grad"][1])),
+}
+
 # frame selection by committee deviation (include/htf_select.h; hoomd_tf_amd/select.py DeviationSelector)
 SEL_FIRST, SEL_LARGEST = 0, 1
 SEL_FORCE, SEL_ENERGY = 0, 1
@@ -354,7 +360,8 @@ SEL_PROTOTYPES = {
 # every table above: what the ctypes and the pybind11 binding both declare
 ALL_PROTOTYPES = tuple((name, proto) for table in (PROTOTYPES, STANDIN_PROTOTYPES, STEP_CHECK_PROTOTYPES, CG_PROTOTYPES, GEOM_PROTOTYPES, NLIST_PROTOTYPES,
                                                    BP_PROTOTYPES, CF_PROTOTYPES, CT_PROTOTYPES, ANG_PROTOTYPES, AT_PROTOTYPES, CGHOST_PROTOTYPES,
-                                                   CMT_PROTOTYPES, CMT_TRAIN_PROTOTYPES, SEL_PROTOTYPES, CFW_PROTOTYPES, CFWT_PROTOTYPES)
+                                                   CMT_PROTOTYPES, CMT_TRAIN_PROTOTYPES, SEL_PROTOTYPES, CFW_PROTOTYPES, CFWT_PROTOTYPES,
+                                                   CFW16_PROTOTYPES)
                        for name, proto in table.items())
 
 

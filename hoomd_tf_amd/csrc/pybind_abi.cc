@@ -28,6 +28,7 @@
 #include "htf_select.h"
 #include "htf_cfwide.h"
 #include "htf_cfwtrain.h"
+#include "htf_cfwide16.h"
 
 namespace py = pybind11;
 
@@ -247,6 +248,10 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
     X(htf_cfw_scratch_floats) \
     X(htf_cfw_loss_grad)
 
+// include/htf_cfwide16.h: the same pass 1 on the fp16 matrix instruction with split operands (_lib.CFW16_PROTOTYPES)
+#define HTF_CFW16_FUNCTIONS(X) \
+    X(htf_cfw16_grad)
+
 PYBIND11_MODULE(_htf_abi, m) {
     m.doc() = "pybind11 binding of libhtf_amd.so's C ABI: pointers as integers";
     // a stale module (or library): this module's templates were instantiated from one header, the library it resolved at load
@@ -272,5 +277,6 @@ PYBIND11_MODULE(_htf_abi, m) {
     HTF_SEL_FUNCTIONS(X)
     HTF_CFW_FUNCTIONS(X)
     HTF_CFWT_FUNCTIONS(X)
+    HTF_CFW16_FUNCTIONS(X)
 #undef X
 }

@@ -416,7 +416,27 @@ class DescriptorMLP:
     layer; up to 64 units ``total_loss_gradient`` (``dense="lanes"``) is the faster sweep.  Not covered on
     the wide stack: angular channels, committees, slab domains (``n_ghost``; a ``SlabDomain`` run raises), and the row-operator
     sweep ``loss_gradient``.
-    Limits: ``n_types * K * (1 + l_max) <= 64``, ``H1, H2 <= 64`` (256 with ``dense="mfma"``), at most 256 neighbor slots."""
+
+    ``dense="split16"`` (with ``conservative=True``; htf_cfw16_grad, include/htf_cfwide16.h) is ``dense="mfma"``'s first sweep on
+    the fp16 matrix instruction, for evaluation: the same tile, weights, ``w`` and weights API, widths ``1 <= H1, H2 <= 256``,
+    ``n_species``, ``r_cut``, both activations and pair dtypes, ``virial``, ``n_ghost`` / ``halo``.  Every operand of a matrix
+    product travels as ``x = hi + lo`` in fp16 (both rounded to nearest) and a step is the three products ``lo hi + hi lo + hi hi``
+    on ``v_mfma_f32_32x32x16_f16`` with fp32 accumulators, as ``PairMLP(precision="split16")``; ``G_i`` has the row kernel's bits
+    before it is split; the activation function, ``E_i`` and ``g_i`` are fp32, the tile's images of ``h1``, ``dz2`` and ``dz1`` are
+    fp16 hi + lo pairs like every other operand; and the weights are split in registers as they stream from
+    L2, so nothing is cached between calls.  Forces and energies are held to the fp32 stack's own tolerance
+    (tests/test_gpu_desc_split16.py).  Range: an operand beyond fp16's largest number (``|x| > 65504``: a weight, or with
+    ``activation="linear"`` a hidden value) makes the energy of the rows it enters, and what of their ``g_i`` depends on it,
+    NaN or infinite, never a wrong finite value.  Evaluation only: ``trainable`` other than ``False`` raises and names
+    ``trainable="wide"``; ``l_max > 0``, ``n_models > 1`` and ``forces`` / ``loss_gradient`` / ``total_loss_gradient`` raise as for
+    ``"mfma"``; ``wide_loss_gradient`` stays callable, so a layer can be fitted offline in fp32 and run in split16.
+    When: measured on the MI355X (DESIGN.md 0.14, 131 072 rows x 128 slots) the first sweep takes 0.79 ms against ``"mfma"``'s
+    0.87 ms at 256 x 256, so ``"split16"`` is the faster stack for evaluation only at the top widths, by 10 %, not by the factor
+    the fp16 matrix rate suggests.  At 128 x 128 the two are level (0.59 ms); at 64 x 64 and 32 x 32 ``"split16"`` is slower than
+    ``"mfma"`` (0.41 / 0.40 and 0.39 / 0.37 ms) and both are slower than ``"lanes"`` (0.31 and 0.25 ms), which stays the default and
+    the recommendation up to 64 units.  ``"split16"`` is not recommended below about 200 units.
+    Limits: ``n_types * K * (1 + l_max) <= 64``, ``H1, H2 <= 64`` (256 with ``dense="mfma"`` or ``"split16"``), at most 256
+    neighbor slots."""
 
     name = 'descriptor-mlp'
     _KEYS = ("W1", "b1", "W2", "b2", "W3", "b3")
@@ -433,8 +453,8 @@ class DescriptorMLP:
         wide = isinstance(trainable, str) and trainable == "wide"
         if wide:
             dense = "mfma"   # the sweep of the wide stack, fitted and run alike (include/htf_cfwtrain.h)
-        if dense not in ("lanes", "mfma"):
-            raise ValueError("DescriptorMLP: dense must be 'lanes' or 'mfma', not %r" % (dense,))
+        if dense not in ("lanes", "mfma", "split16"):
+            raise ValueError("DescriptorMLP: dense must be 'lanes', 'mfma' or 'split16', not %r" % (dense,))
         self.dense = dense
         if isinstance(l_max, bool) or int(l_max) != l_max or int(l_max) not in (0, 1, 2):
             raise ValueError("DescriptorMLP: l_max must be 0, 1 or 2, not %r" % (l_max,))
@@ -512,10 +532,22 @@ class DescriptorMLP:
                                  "sweeps keep one hidden unit per lane; dense=\"lanes\" with H1, H2 <= %d runs them"
                                  % ("l_max = %d" % l_max if l_max else "n_models = %d" % n_models if n_models > 1
                                     else "trainable=%r" % (trainable,), self.MAX_H))
-        max_h = self.MAX_H_MFMA if dense == "mfma" else self.MAX_H
+        if dense == "split16":
+            if self.trainable:
+                raise ValueError("DescriptorMLP: dense=\"split16\" is evaluation only and does not go with trainable=%r: "
+                                 "trainable=\"wide\" (dense=\"mfma\") fits the wide stack in fp32, and wide_loss_gradient is "
+                                 "callable on this layer offline" % (trainable,))
+            if not self.conservative:
+                raise ValueError("DescriptorMLP: dense=\"split16\" needs conservative=True: it is the first sweep of total_forces "
+                                 "(include/htf_cfwide16.h); the row operator has no matrix form")
+            if l_max or n_models > 1:
+                raise ValueError("DescriptorMLP: dense=\"split16\" does not go with %s: the angular and committee sweeps keep one "
+                                 "hidden unit per lane; dense=\"lanes\" with H1, H2 <= %d runs them"
+                                 % ("l_max = %d" % l_max if l_max else "n_models = %d" % n_models, self.MAX_H))
+        max_h = self.MAX_H_MFMA if dense != "lanes" else self.MAX_H
         if not (1 <= H1 <= max_h and 1 <= H2 <= max_h):
             raise ValueError("DescriptorMLP: hidden widths %d, %d outside [1, %d]%s" % (
-                H1, H2, max_h, "" if dense == "mfma" else
+                H1, H2, max_h, "" if dense != "lanes" else
                 "; conservative=True with dense=\"mfma\" takes up to %d" % self.MAX_H_MFMA))
         rbf = RBFExpansion(low, high, K)
         if not rbf.gap > 0:
@@ -577,10 +609,10 @@ class DescriptorMLP:
         return lay
 
     def _no_mfma(self, what):
-        if self.dense == "mfma":
-            raise NotImplementedError("DescriptorMLP: %s() keeps one hidden unit per lane and has no MFMA form (dense=\"mfma\"): "
+        if self.dense != "lanes":
+            raise NotImplementedError("DescriptorMLP: %s() keeps one hidden unit per lane and has no MFMA form (dense=\"%s\"): "
                                       "total_forces(x, index) evaluates this layer; dense=\"lanes\" with H1, H2 <= %d has %s()"
-                                      % (what, self.MAX_H, what))
+                                      % (what, self.dense, self.MAX_H, what))
 
     def _no_committee(self, what):
         if self.n_models > 1:
@@ -824,6 +856,9 @@ class DescriptorMLP:
             own1, own2 = (self.l_max,), (self.l_max, B + n_ghost)
         elif self.dense == "mfma":   # include/htf_cfwide.h: pass 1 on the matrix instruction, the same table; pass 2 as below
             grad, forces, table, e = lib.htf_cfw_grad, lib.htf_cf_forces_ghost, f32(B + n_ghost, self.D), f32(B)
+            own1, own2 = (), (B + n_ghost,)
+        elif self.dense == "split16":   # include/htf_cfwide16.h: the same pass 1 on the fp16 matrix instruction, split operands
+            grad, forces, table, e = lib.htf_cfw16_grad, lib.htf_cf_forces_ghost, f32(B + n_ghost, self.D), f32(B)
             own1, own2 = (), (B + n_ghost,)
         else:            # include/htf_cforce.h; pass 2 by include/htf_cghost.h, whose n_table = B is the plain entry
             grad, forces, table, e = lib.htf_cf_grad, lib.htf_cf_forces_ghost, f32(B + n_ghost, self.D), f32(B)

@@ -19,7 +19,9 @@ M members at once, one wave per member on the same rows: include/htf_cmt_train.h
 conservative forces, ``DescriptorMLP(conservative=True, dense="mfma")``, the dense stack of a 64-row tile on the fp32 matrix
 instruction: include/htf_cfwide.h, and ``dense="split16"``, the same tile on the fp16 matrix instruction with operands split as
 hi + lo: include/htf_cfwide16.h; force matching for those networks, ``DescriptorMLP(trainable="wide")`` and
-``wide_loss_gradient``, the sweep of a 32-row tile with (value | tangent) images on the same instruction: include/htf_cfwtrain.h).
+``wide_loss_gradient``, the sweep of a 32-row tile with (value | tangent) images on the same instruction: include/htf_cfwtrain.h; a third hidden layer on that stack for evaluation,
+``DescriptorMLP(conservative=True, dense="mfma", H3=h)``, a tile of 64 or 32 rows by what its images need of LDS:
+include/htf_cfwide3.h).
 The offline path ``iter_from_trajectory`` / ``ArrayTrajectory`` runs a
 ``SimModel`` over stored frames.
 ``DeviationSelector`` consumes the committee's deviation where it is produced: ``sel.update(layer.deviation, positions, box)``

@@ -346,6 +346,12 @@ CFW16_PROTOTYPES = {
     "htf_cfw16_grad": (_i, list(CF_PROTOTYPES["htf_cf_grad"][1])),
 }
 
+# pass 1 for three hidden layers on the fp32 matrix instruction (include/htf_cfwide3.h; DescriptorMLP(dense="mfma", H3=...)):
+# htf_cfw_grad's arguments with H3 after H2
+CFW3_PROTOTYPES = {
+    "htf_cfw3_grad": (_i, CF_PROTOTYPES["htf_cf_grad"][1][:8] + [_u] + CF_PROTOTYPES["htf_cf_grad"][1][8:]),
+}
+
 # frame selection by committee deviation (include/htf_select.h; hoomd_tf_amd/select.py DeviationSelector)
 SEL_FIRST, SEL_LARGEST = 0, 1
 SEL_FORCE, SEL_ENERGY = 0, 1
@@ -361,7 +367,7 @@ SEL_PROTOTYPES = {
 ALL_PROTOTYPES = tuple((name, proto) for table in (PROTOTYPES, STANDIN_PROTOTYPES, STEP_CHECK_PROTOTYPES, CG_PROTOTYPES, GEOM_PROTOTYPES, NLIST_PROTOTYPES,
                                                    BP_PROTOTYPES, CF_PROTOTYPES, CT_PROTOTYPES, ANG_PROTOTYPES, AT_PROTOTYPES, CGHOST_PROTOTYPES,
                                                    CMT_PROTOTYPES, CMT_TRAIN_PROTOTYPES, SEL_PROTOTYPES, CFW_PROTOTYPES, CFWT_PROTOTYPES,
-                                                   CFW16_PROTOTYPES)
+                                                   CFW16_PROTOTYPES, CFW3_PROTOTYPES)
                        for name, proto in table.items())
 
 

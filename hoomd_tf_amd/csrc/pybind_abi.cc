@@ -29,6 +29,7 @@
 #include "htf_cfwide.h"
 #include "htf_cfwtrain.h"
 #include "htf_cfwide16.h"
+#include "htf_cfwide3.h"
 
 namespace py = pybind11;
 
@@ -252,6 +253,10 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
 #define HTF_CFW16_FUNCTIONS(X) \
     X(htf_cfw16_grad)
 
+// include/htf_cfwide3.h: pass 1 for three hidden layers on the fp32 matrix instruction (_lib.CFW3_PROTOTYPES)
+#define HTF_CFW3_FUNCTIONS(X) \
+    X(htf_cfw3_grad)
+
 PYBIND11_MODULE(_htf_abi, m) {
     m.doc() = "pybind11 binding of libhtf_amd.so's C ABI: pointers as integers";
     // a stale module (or library): this module's templates were instantiated from one header, the library it resolved at load
@@ -278,5 +283,6 @@ PYBIND11_MODULE(_htf_abi, m) {
     HTF_CFW_FUNCTIONS(X)
     HTF_CFWT_FUNCTIONS(X)
     HTF_CFW16_FUNCTIONS(X)
+    HTF_CFW3_FUNCTIONS(X)
 #undef X
 }

@@ -435,6 +435,22 @@ class DescriptorMLP:
     the fp16 matrix rate suggests.  At 128 x 128 the two are level (0.59 ms); at 64 x 64 and 32 x 32 ``"split16"`` is slower than
     ``"mfma"`` (0.41 / 0.40 and 0.39 / 0.37 ms) and both are slower than ``"lanes"`` (0.31 and 0.25 ms), which stays the default and
     the recommendation up to 64 units.  ``"split16"`` is not recommended below about 200 units.
+
+    ``H3=h`` (``1 <= h <= 256``, with ``conservative=True`` and ``dense="mfma"``; htf_cfw3_grad, include/htf_cfwide3.h) adds a
+    third hidden layer, the depth of ANI (160-128-96) and DeepMD (240-240-240) fitting networks: ``E_i = W4^T act(W3^T act(W2^T
+    act(W1^T G_i + b1) + b2) + b3) + b4``.  The weights are eight Keras arrays, ``W1 [D, H1], b1, W2 [H1, H2], b2, W3 [H2, H3],
+    b3, W4 [H3, 1], b4``, flat in ``w`` (``P = D H1 + H1 + H1 H2 + H2 + H2 H3 + H3 + H3 + 1`` floats per network), drawn by
+    ``mlp_params(seed + s, K=D, H1, H2, H3=h)``, and ``get_weights`` / ``set_weights`` / ``save_weights`` / ``load_weights``
+    and the species axis carry all eight.  The first sweep of ``total_forces`` is ``dense="mfma"``'s with a tile of its own --
+    ``h2`` kept for the reverse pass, ``dz3`` in the lines ``G`` leaves free, 64 rows while the tile's images fit the compute
+    unit's LDS and 32 rows above (240^3, 256^3) -- and writes the same ``g`` and ``E`` tables, so the second sweep,
+    ``n_species``, ``r_cut``, both activations and pair dtypes, ``virial``, ``n_ghost`` / ``halo``, ``compute_nlist_forces``
+    and ``tfcompute`` work unchanged.  Evaluation only, each raising ``NotImplementedError``: ``trainable`` other than
+    ``False`` (``"wide"`` included: the force-matching sweep for three layers is a follow-up), ``dense="split16"``, ``l_max >
+    0``, ``n_models > 1``, and ``forces`` / ``loss_gradient`` / ``total_loss_gradient`` / ``wide_loss_gradient``;
+    ``descriptor`` works.  Measured (DESIGN.md 0.15, 131 072 rows x 128 slots): the first sweep takes 0.44 / 0.76 / 1.86 ms at
+    64^3 / 128^3 / 256^3 against 0.41 / 0.59 / 0.88 ms for two hidden layers of the same widths.  ``H3=None`` is the layer
+    without the argument.
     Limits: ``n_types * K * (1 + l_max) <= 64``, ``H1, H2 <= 64`` (256 with ``dense="mfma"`` or ``"split16"``), at most 256
     neighbor slots."""
 
@@ -448,8 +464,12 @@ class DescriptorMLP:
     l1_reg = (0.0,)
 
     def __init__(self, K=16, H1=32, H2=32, low=0.0, high=3.0, n_types=1, activation="tanh", seed=3, device=None,
-                 trainable=False, r_cut=None, n_species=1, conservative=False, l_max=0, n_models=1, dense="lanes"):
+                 trainable=False, r_cut=None, n_species=1, conservative=False, l_max=0, n_models=1, dense="lanes", H3=None):
         K, H1, H2, n_types, n_species = int(K), int(H1), int(H2), int(n_types), int(n_species)
+        if H3 is not None and (isinstance(H3, bool) or not isinstance(H3, (int, np.integer)) or not 1 <= int(H3) <= self.MAX_H_MFMA):
+            raise ValueError("DescriptorMLP: H3 must be an integer in [1, %d] (None: two hidden layers), not %r; it needs "
+                             "conservative=True and dense=\"mfma\"" % (self.MAX_H_MFMA, H3))
+        self.H3 = H3 = None if H3 is None else int(H3)
         wide = isinstance(trainable, str) and trainable == "wide"
         if wide:
             dense = "mfma"   # the sweep of the wide stack, fitted and run alike (include/htf_cfwtrain.h)
@@ -464,6 +484,17 @@ class DescriptorMLP:
             raise ValueError("DescriptorMLP: n_models must be an integer in [1, %d], not %r: a larger committee is several "
                              "layers, each evaluated with its own total_forces" % (self.MAX_MODELS, n_models))
         self.n_models = n_models = int(n_models)
+        if H3 is not None:   # include/htf_cfwide3.h: evaluation on the fp32 matrix instruction, nothing else yet
+            for bad, what in ((l_max, "l_max = %d" % l_max), (n_models > 1, "n_models = %d" % n_models),
+                              (dense == "split16", "dense=\"split16\""),
+                              (trainable is not False, "trainable=%r" % (trainable,))):
+                if bad:
+                    raise NotImplementedError("DescriptorMLP: H3 = %d does not go with %s: the three-hidden-layer stack is "
+                                              "evaluation on the fp32 matrix instruction only; the two-hidden-layer layer "
+                                              "(H3=None) covers it" % (H3, what))
+            if not conservative or dense != "mfma":
+                raise ValueError("DescriptorMLP: H3 = %d needs conservative=True and dense=\"mfma\": the third hidden layer is "
+                                 "the first sweep of total_forces on the matrix instruction (include/htf_cfwide3.h)" % H3)
         committee = isinstance(trainable, str) and trainable == "committee"
         if committee:
             if n_models < 2:
@@ -570,7 +601,9 @@ class DescriptorMLP:
                                  "of LDS, above the %d bytes of one compute unit: fewer members, or narrower networks; "
                                  "member(m, trainable=\"total\") trains one member at a time"
                                  % (n_models, self.D, H1, H2, need, self.MAX_COMMITTEE_LDS))
-        ps = [mlp_params(seed=seed + s, K=self.D, H1=H1, H2=H2) for s in range(n_models * n_species)]   # [M][S]
+        if H3 is not None:
+            self._KEYS = self._KEYS + ("W4", "b4")   # eight Keras arrays: W3 is [H2, H3], W4 [H3, 1]
+        ps = [mlp_params(seed=seed + s, K=self.D, H1=H1, H2=H2, H3=H3) for s in range(n_models * n_species)]   # [M][S]
         self._shapes = [ps[0][k].shape for k in self._KEYS]
         self.P = sum(int(np.prod(sh)) for sh in self._shapes)   # floats of one network
         self.w = torch.tensor(np.concatenate([p[k].ravel() for p in ps for k in self._KEYS]), dtype=torch.float32, device=device)
@@ -609,10 +642,17 @@ class DescriptorMLP:
         return lay
 
     def _no_mfma(self, what):
+        self._no_deep(what)
         if self.dense != "lanes":
             raise NotImplementedError("DescriptorMLP: %s() keeps one hidden unit per lane and has no MFMA form (dense=\"%s\"): "
                                       "total_forces(x, index) evaluates this layer; dense=\"lanes\" with H1, H2 <= %d has %s()"
                                       % (what, self.dense, self.MAX_H, what))
+
+    def _no_deep(self, what):
+        if self.H3 is not None:
+            raise NotImplementedError("DescriptorMLP: %s() has no form for three hidden layers (H3 = %d): total_forces(x, index) "
+                                      "evaluates this layer; the two-hidden-layer layer (H3=None) has %s()"
+                                      % (what, self.H3, what))
 
     def _no_committee(self, what):
         if self.n_models > 1:
@@ -623,6 +663,8 @@ class DescriptorMLP:
     def get_config(self):
         cfg = {'K': self.K, 'H1': self.H1, 'H2': self.H2, 'low': self.low, 'high': self.high, 'n_types': self.n_types,
                'activation': self.activation}
+        if self.H3 is not None:
+            cfg['H3'] = self.H3
         if self.trainable:
             cfg['trainable'] = self.trainable   # (True, "total", "angular", "committee" or "wide")
         if self.r_cut is not None:
@@ -640,7 +682,7 @@ class DescriptorMLP:
         return cfg
 
     def get_weights(self):
-        """The six Keras arrays; with ``n_species = S > 1`` each has a leading axis of length S, and with ``n_models = M > 1``
+        """The six Keras arrays (eight with ``H3``); with ``n_species = S > 1`` each has a leading axis of length S, and with ``n_models = M > 1``
         one of length M ahead of it."""
         lead = self._lead_axes()
         flat, out, o = self.w.detach().cpu().numpy().reshape(-1, self.P), [], 0
@@ -737,7 +779,8 @@ class DescriptorMLP:
             self.B, self.NN = self.shape = lay._check(x)
             self.pair = (x.data_ptr(), ops._dt(x))
             self.rbf = (lay.K, lay.n_types, lay.mu.data_ptr(), float(lay.gap))
-            self.widths = (lay.K, lay.n_types, lay.H1, lay.H2, _lib.ACT_TANH if lay.activation == "tanh" else _lib.ACT_LINEAR)
+            self.widths = ((lay.K, lay.n_types, lay.H1, lay.H2) + ((lay.H3,) if lay.H3 is not None else ())   # (htf_cfw3_grad's)
+                           + (_lib.ACT_TANH if lay.activation == "tanh" else _lib.ACT_LINEAR,))
             self.r_cut = float(lay.r_cut or 0.0)
             self.stream = ops._stream(x)
 
@@ -854,6 +897,9 @@ class DescriptorMLP:
             grad, forces, e = lib.htf_ang_grad, lib.htf_ang_forces_ghost, f32(B)
             table = f32(B + n_ghost, self.Dr, 4 if self.l_max == 1 else 10)
             own1, own2 = (self.l_max,), (self.l_max, B + n_ghost)
+        elif self.H3 is not None:   # include/htf_cfwide3.h: pass 1 for three hidden layers, the same table; pass 2 as below
+            grad, forces, table, e = lib.htf_cfw3_grad, lib.htf_cf_forces_ghost, f32(B + n_ghost, self.D), f32(B)
+            own1, own2 = (), (B + n_ghost,)
         elif self.dense == "mfma":   # include/htf_cfwide.h: pass 1 on the matrix instruction, the same table; pass 2 as below
             grad, forces, table, e = lib.htf_cfw_grad, lib.htf_cf_forces_ghost, f32(B + n_ghost, self.D), f32(B)
             own1, own2 = (), (B + n_ghost,)
@@ -1010,6 +1056,7 @@ class DescriptorMLP:
         ``l_max = 0`` layer, whatever its ``dense`` and ``trainable``; angular channels, committees and slab domains are not
         covered."""
         self._no_committee("wide_loss_gradient")
+        self._no_deep("wide_loss_gradient")
         if self.l_max:
             raise NotImplementedError("DescriptorMLP: wide_loss_gradient() is the sweep of an l_max = 0 layer; with l_max = %d "
                                       "angular_loss_gradient(x, labels, index) is the force-matching sweep (dense=\"lanes\")"

@@ -21,7 +21,8 @@ instruction: include/htf_cfwide.h, and ``dense="split16"``, the same tile on the
 hi + lo: include/htf_cfwide16.h; force matching for those networks, ``DescriptorMLP(trainable="wide")`` and
 ``wide_loss_gradient``, the sweep of a 32-row tile with (value | tangent) images on the same instruction: include/htf_cfwtrain.h; a third hidden layer on that stack for evaluation,
 ``DescriptorMLP(conservative=True, dense="mfma", H3=h)``, a tile of 64 or 32 rows by what its images need of LDS:
-include/htf_cfwide3.h).
+include/htf_cfwide3.h; and force matching for it, ``DescriptorMLP(trainable="deep", H3=h)`` and ``deep_loss_gradient``, four
+(value | tangent) images on a tile of 32 or 16 rows: include/htf_cfw3train.h).
 The offline path ``iter_from_trajectory`` / ``ArrayTrajectory`` runs a
 ``SimModel`` over stored frames.
 ``DeviationSelector`` consumes the committee's deviation where it is produced: ``sel.update(layer.deviation, positions, box)``

@@ -352,6 +352,13 @@ CFW3_PROTOTYPES = {
     "htf_cfw3_grad": (_i, CF_PROTOTYPES["htf_cf_grad"][1][:8] + [_u] + CF_PROTOTYPES["htf_cf_grad"][1][8:]),
 }
 
+# force matching for three hidden layers (include/htf_cfw3train.h; DescriptorMLP.deep_loss_gradient, trainable="deep"):
+# htf_cfw_loss_grad's arguments with H3 after H2
+CFW3T_PROTOTYPES = {
+    "htf_cfw3_scratch_floats": (C.c_size_t, [_u, _u, _u, _u, _u, _u]),
+    "htf_cfw3_loss_grad": (_i, CT_PROTOTYPES["htf_ct_loss_grad"][1][:9] + [_u] + CT_PROTOTYPES["htf_ct_loss_grad"][1][9:]),
+}
+
 # frame selection by committee deviation (include/htf_select.h; hoomd_tf_amd/select.py DeviationSelector)
 SEL_FIRST, SEL_LARGEST = 0, 1
 SEL_FORCE, SEL_ENERGY = 0, 1
@@ -367,7 +374,7 @@ SEL_PROTOTYPES = {
 ALL_PROTOTYPES = tuple((name, proto) for table in (PROTOTYPES, STANDIN_PROTOTYPES, STEP_CHECK_PROTOTYPES, CG_PROTOTYPES, GEOM_PROTOTYPES, NLIST_PROTOTYPES,
                                                    BP_PROTOTYPES, CF_PROTOTYPES, CT_PROTOTYPES, ANG_PROTOTYPES, AT_PROTOTYPES, CGHOST_PROTOTYPES,
                                                    CMT_PROTOTYPES, CMT_TRAIN_PROTOTYPES, SEL_PROTOTYPES, CFW_PROTOTYPES, CFWT_PROTOTYPES,
-                                                   CFW16_PROTOTYPES, CFW3_PROTOTYPES)
+                                                   CFW16_PROTOTYPES, CFW3_PROTOTYPES, CFW3T_PROTOTYPES)
                        for name, proto in table.items())
 
 

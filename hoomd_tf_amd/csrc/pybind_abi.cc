@@ -30,6 +30,7 @@
 #include "htf_cfwtrain.h"
 #include "htf_cfwide16.h"
 #include "htf_cfwide3.h"
+#include "htf_cfw3train.h"
 
 namespace py = pybind11;
 
@@ -257,6 +258,11 @@ void bind(py::module &m, const char *name, R (*fn)(A...)) {
 #define HTF_CFW3_FUNCTIONS(X) \
     X(htf_cfw3_grad)
 
+// include/htf_cfw3train.h: force matching for three hidden layers on the fp32 matrix instruction (_lib.CFW3T_PROTOTYPES)
+#define HTF_CFW3T_FUNCTIONS(X) \
+    X(htf_cfw3_scratch_floats) \
+    X(htf_cfw3_loss_grad)
+
 PYBIND11_MODULE(_htf_abi, m) {
     m.doc() = "pybind11 binding of libhtf_amd.so's C ABI: pointers as integers";
     // a stale module (or library): this module's templates were instantiated from one header, the library it resolved at load
@@ -284,5 +290,6 @@ PYBIND11_MODULE(_htf_abi, m) {
     HTF_CFWT_FUNCTIONS(X)
     HTF_CFW16_FUNCTIONS(X)
     HTF_CFW3_FUNCTIONS(X)
+    HTF_CFW3T_FUNCTIONS(X)
 #undef X
 }

@@ -445,12 +445,24 @@ class DescriptorMLP:
     ``h2`` kept for the reverse pass, ``dz3`` in the lines ``G`` leaves free, 64 rows while the tile's images fit the compute
     unit's LDS and 32 rows above (240^3, 256^3) -- and writes the same ``g`` and ``E`` tables, so the second sweep,
     ``n_species``, ``r_cut``, both activations and pair dtypes, ``virial``, ``n_ghost`` / ``halo``, ``compute_nlist_forces``
-    and ``tfcompute`` work unchanged.  Evaluation only, each raising ``NotImplementedError``: ``trainable`` other than
-    ``False`` (``"wide"`` included: the force-matching sweep for three layers is a follow-up), ``dense="split16"``, ``l_max >
-    0``, ``n_models > 1``, and ``forces`` / ``loss_gradient`` / ``total_loss_gradient`` / ``wide_loss_gradient``;
-    ``descriptor`` works.  Measured (DESIGN.md 0.15, 131 072 rows x 128 slots): the first sweep takes 0.44 / 0.76 / 1.86 ms at
-    64^3 / 128^3 / 256^3 against 0.41 / 0.59 / 0.88 ms for two hidden layers of the same widths.  ``H3=None`` is the layer
-    without the argument.
+    and ``tfcompute`` work unchanged.  Each raising ``NotImplementedError``: ``trainable`` other than ``False`` and
+    ``"deep"``, ``dense="split16"``, ``l_max > 0``, ``n_models > 1``, and ``forces`` / ``loss_gradient`` /
+    ``total_loss_gradient`` / ``wide_loss_gradient``; ``descriptor`` works.  Measured (DESIGN.md 0.15, 131 072 rows x 128
+    slots): the first sweep takes 0.44 / 0.76 / 1.86 ms at 64^3 / 128^3 / 256^3 against 0.41 / 0.59 / 0.88 ms for two hidden
+    layers of the same widths.  ``H3=None`` is the layer without the argument.
+
+    ``trainable="deep"`` (htf_cfw3_loss_grad, include/htf_cfw3train.h) is force matching for the three-hidden-layer stack: it
+    needs ``H3`` and implies ``conservative=True`` and ``dense="mfma"``, as ``"wide"`` does for two layers.  Under
+    ``tfcompute.attach(..., train=True)`` every step is one ``deep_loss_gradient`` sweep on the step's own list, index and
+    ``total_forces`` output, and one optimizer step (one per species present); offline, ``deep_loss_gradient(x, labels,
+    index)``, callable on any ``H3`` layer.  The sweep is ``wide_loss_gradient``'s with a tile of its own: four (value | tangent)
+    LDS images (``h2`` and its tangent kept for the reverse pass), 32 rows while they fit the compute unit's LDS and 16 rows
+    above 608 image lines (240^3, 256^3), where a line's 16 value and 16 tangent columns share one matrix instruction; no
+    atomics, the same bits at every call.  It is the value for every network with ``H3``; what it costs (DESIGN.md 0.16,
+    131 072 rows x 128 slots): 1.02 / 1.66 / 1.77 ms a sweep at 64^3 / 128^3 / 160-128-96 against the two-layer sweep's 0.80 /
+    1.11 / 1.28 ms at the same ``H1 x H2``, and 6.21 / 6.62 ms at 240^3 / 256^3 against 2.25 / 2.36 ms -- twice the dense
+    arithmetic in 2.8 times the time on the 16-row tile, which also adds into its partial twice as often.  Scratch up to 152 MB
+    (256 partials).  Not covered: slab domains (a ``SlabDomain`` run raises), committees, angular channels, the fp16 pipe.
     Limits: ``n_types * K * (1 + l_max) <= 64``, ``H1, H2 <= 64`` (256 with ``dense="mfma"`` or ``"split16"``), at most 256
     neighbor slots."""
 
@@ -473,6 +485,13 @@ class DescriptorMLP:
         wide = isinstance(trainable, str) and trainable == "wide"
         if wide:
             dense = "mfma"   # the sweep of the wide stack, fitted and run alike (include/htf_cfwtrain.h)
+        deep = isinstance(trainable, str) and trainable == "deep"
+        if deep:
+            if H3 is None:
+                raise ValueError("DescriptorMLP: trainable=\"deep\" is force matching for three hidden layers and needs H3 "
+                                 "(include/htf_cfw3train.h); trainable=\"wide\" fits the two-hidden-layer stack")
+            if dense != "split16":   # (which H3 refuses below)
+                conservative, dense = True, "mfma"   # the sweep of the deep stack, fitted and run alike
         if dense not in ("lanes", "mfma", "split16"):
             raise ValueError("DescriptorMLP: dense must be 'lanes', 'mfma' or 'split16', not %r" % (dense,))
         self.dense = dense
@@ -484,10 +503,10 @@ class DescriptorMLP:
             raise ValueError("DescriptorMLP: n_models must be an integer in [1, %d], not %r: a larger committee is several "
                              "layers, each evaluated with its own total_forces" % (self.MAX_MODELS, n_models))
         self.n_models = n_models = int(n_models)
-        if H3 is not None:   # include/htf_cfwide3.h: evaluation on the fp32 matrix instruction, nothing else yet
+        if H3 is not None:   # include/htf_cfwide3.h on the fp32 matrix instruction; fitted by trainable="deep" alone
             for bad, what in ((l_max, "l_max = %d" % l_max), (n_models > 1, "n_models = %d" % n_models),
                               (dense == "split16", "dense=\"split16\""),
-                              (trainable is not False, "trainable=%r" % (trainable,))):
+                              (trainable is not False and not deep, "trainable=%r" % (trainable,))):
                 if bad:
                     raise NotImplementedError("DescriptorMLP: H3 = %d does not go with %s: the three-hidden-layer stack is "
                                               "evaluation on the fp32 matrix instruction only; the two-hidden-layer layer "
@@ -518,9 +537,9 @@ class DescriptorMLP:
                 raise ValueError("DescriptorMLP: n_models = %d needs conservative=True: the deviation is defined on the forces "
                                  "of the total energy (total_forces)" % n_models)
         if isinstance(trainable, str):
-            if trainable not in ("total", "angular", "committee", "wide"):
-                raise ValueError("DescriptorMLP: trainable must be False, True, 'total', 'angular', 'committee' or 'wide', not %r"
-                                 % (trainable,))
+            if trainable not in ("total", "angular", "committee", "wide", "deep"):
+                raise ValueError("DescriptorMLP: trainable must be False, True, 'total', 'angular', 'committee', 'wide' or 'deep', "
+                                 "not %r" % (trainable,))
             if trainable == "angular" and not l_max:
                 raise ValueError("DescriptorMLP: trainable=\"angular\" fits the angular channels and needs l_max = 1 or 2; "
                                  "trainable=\"total\" fits the conservative forces of an l_max = 0 layer")
@@ -558,7 +577,7 @@ class DescriptorMLP:
             if not self.conservative:
                 raise ValueError("DescriptorMLP: dense=\"mfma\" needs conservative=True: it is the first sweep of total_forces "
                                  "(include/htf_cfwide.h); the row operator has no MFMA form")
-            if l_max or n_models > 1 or (self.trainable and not wide):
+            if l_max or n_models > 1 or (self.trainable and not (wide or deep)):
                 raise ValueError("DescriptorMLP: dense=\"mfma\" does not go with %s: the angular, committee and force-matching "
                                  "sweeps keep one hidden unit per lane; dense=\"lanes\" with H1, H2 <= %d runs them"
                                  % ("l_max = %d" % l_max if l_max else "n_models = %d" % n_models if n_models > 1
@@ -666,7 +685,7 @@ class DescriptorMLP:
         if self.H3 is not None:
             cfg['H3'] = self.H3
         if self.trainable:
-            cfg['trainable'] = self.trainable   # (True, "total", "angular", "committee" or "wide")
+            cfg['trainable'] = self.trainable   # (True, "total", "angular", "committee", "wide" or "deep")
         if self.r_cut is not None:
             cfg['r_cut'] = self.r_cut
         if self.n_species != 1:
@@ -1068,6 +1087,32 @@ class DescriptorMLP:
             scratch_floats=lambda n: lib.htf_cfw_scratch_floats(n, self.K, self.n_types, self.H1, self.H2))
         rho = torch.sub(buffers[0].detach(), labels.detach().to(torch.float32)).contiguous()
         return self._sweep(lib.htf_cfw_loss_grad, a, index, rho, buffers, ())
+
+    def deep_loss_gradient(self, x, labels, index, types=None, pred=None, accum=None, species=None):
+        """``wide_loss_gradient`` for a layer with three hidden layers (``H3``; htf_cfw3_loss_grad,
+        include/htf_cfw3train.h): one force-matching sweep on the forces of the total energy of ``D -> H1 -> H2 -> H3 -> 1``,
+        widths up to 256.  Argument for argument the same: ``accum`` [1 + P], or [S, 1 + P] with zero rows for absent species,
+        holds {SSR, d SSR / d theta} per network in the order of the eight flat weight arrays, for the residuals of
+        ``total_forces(x, index, ...)`` against ``labels`` [B, 4]; ``pred`` [B, 4] fp32 is ``total_forces`` at the current
+        weights, evaluated here (with ``types``) when not given; the residual is formed in fp32 with torch and every row's is
+        read; a slot whose index is outside ``[0, B)`` has no reverse term.  Tiles of 32 rows with four (value | tangent) LDS
+        images, 16 rows where those do not fit the compute unit's LDS (more than 608 image lines: 240^3, 256^3).  Two calls on
+        the same inputs give the same bits.  Callable on any layer with ``H3``, trainable or not; without ``H3`` it raises."""
+        self._no_committee("deep_loss_gradient")
+        if self.l_max:
+            raise NotImplementedError("DescriptorMLP: deep_loss_gradient() is the sweep of an l_max = 0 layer; with l_max = %d "
+                                      "angular_loss_gradient(x, labels, index) is the force-matching sweep (dense=\"lanes\")"
+                                      % self.l_max)
+        if self.H3 is None:
+            raise ValueError("DescriptorMLP: deep_loss_gradient() is the sweep of three hidden layers (H3); wide_loss_gradient(x, "
+                             "labels, index) or total_loss_gradient(x, labels, index) is the sweep of this two-hidden-layer layer")
+        a = self._Args(self, x)
+        index = self._slot_index(index, x)
+        buffers = self._sweep_buffers(
+            x, labels, pred, accum, species, lambda: self.total_forces(x, index, types=types, species=species),
+            scratch_floats=lambda n: lib.htf_cfw3_scratch_floats(n, self.K, self.n_types, self.H1, self.H2, self.H3))
+        rho = torch.sub(buffers[0].detach(), labels.detach().to(torch.float32)).contiguous()
+        return self._sweep(lib.htf_cfw3_loss_grad, a, index, rho, buffers, ())
 
     def committee_loss_gradient(self, x, labels, index, types=None, pred=None, accum=None, species=None):
         """``total_loss_gradient`` for every member of a committee in one sweep (htf_cmt_loss_grad, include/htf_cmt_train.h):

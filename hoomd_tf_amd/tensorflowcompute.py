@@ -465,6 +465,11 @@ class tfcompute:
                 raise NotImplementedError("a DescriptorMLP with trainable=\"wide\" does not train over slab domains yet "
                                           "(n_ghost = %d): wide_loss_gradient has no ghost rows" % ghost["n_ghost"])
             return layer.wide_loss_gradient(nlist_t, labels, entry["index"], types=entry.get("types"), pred=pred, species=species)
+        if layer.trainable == "deep":
+            if ghost["n_ghost"]:
+                raise NotImplementedError("a DescriptorMLP with trainable=\"deep\" does not train over slab domains yet "
+                                          "(n_ghost = %d): deep_loss_gradient has no ghost rows" % ghost["n_ghost"])
+            return layer.deep_loss_gradient(nlist_t, labels, entry["index"], types=entry.get("types"), pred=pred, species=species)
         if layer.trainable == "angular":
             return layer.angular_loss_gradient(nlist_t, labels, entry["index"], types=entry.get("types"), pred=pred, species=species,
                                                **ghost)
